@@ -7,6 +7,16 @@ per GPU (RCCL over xGMI). Measures W untimed warmup steps, then exactly K
 steps bracketed by barrier + torch.cuda.synchronize() on both sides, takes
 the MAX elapsed over ranks, and rank 0 prints ONE JSON line.
 
+A plain run does only that: set up, warm up, time the K steps, print. Two
+options add to it:
+    --dump-outputs DIR  rank 0 writes the loss, logits and updated parameters
+                        of the last timed step as DIR/<name>.npy (float32,
+                        seeded samples of the large tensors) so two builds
+                        can be compared output for output; the inputs are
+                        seeded and identical from run to run
+    --full              everything the benchmark measures beyond the headline
+                        figure belongs behind this flag (nothing today)
+
 Metric/config per BASELINE.json: tokens/sec (whole node), GPT-2 ZeRO-2,
 synthetic data, random-init weights, bf16 compute with fp32 accumulation and
 fp32 optimizer state. Weak scaling: per-GPU batch is fixed as N grows.
@@ -57,6 +67,42 @@ WRAPPERS = {
 }
 
 
+# --dump-outputs sample sizes: 4M logits + 16K per parameter tensor keeps the
+# dump at 24 MB for gpt2-medium (under the 64 MB cap for every preset)
+_DUMP_LOGITS = 1 << 22
+_DUMP_PER_PARAM = 1 << 14
+_DUMP_SEED = 20240
+
+
+def _sample_flat(t, k, gen):
+    """float32 copy of `t` flattened; a fixed seeded sample of k elements
+    (sorted flat indices) when it holds more than k."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > k:
+        idx = torch.randint(0, flat.numel(), (k,), generator=gen)
+        flat = flat[idx.sort().values.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, loss, logits, named_params):
+    """Write what the last timed step handed back: the loss, the logits (None
+    on the fused lm_head path, then omitted) and the updated parameters.
+    The sample indices depend only on the seed and the tensor shapes, so two
+    runs with the same arguments write element-for-element comparable files."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    gen = torch.Generator().manual_seed(_DUMP_SEED)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().cpu().numpy())
+    if logits is not None:
+        np.save(os.path.join(out_dir, "logits.npy"),
+                _sample_flat(logits, _DUMP_LOGITS, gen))
+    params = [_sample_flat(p, _DUMP_PER_PARAM, gen)
+              for _, p in named_params if p.numel() > 0]
+    np.save(os.path.join(out_dir, "params.npy"), np.concatenate(params))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -71,7 +117,23 @@ def main():
                    help="1: row-chunked fused lm_head+CE (-2.75 GB peak, "
                         "+4 ms/step at gpt2-medium b32); 0: materialized "
                         "logits (default, throughput headline)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step computed (loss, logits, updated parameters) "
+                        "as DIR/<name>.npy in float32; large tensors are "
+                        "written as a fixed seeded sample. Rank 0 writes "
+                        "its own view: with more than one GPU under zero1/"
+                        "zero2/zero3 that is rank 0's logits and whatever "
+                        "rank 0 holds of the parameters (shards it does "
+                        "not own may be stale or empty)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements and checks that the "
+                        "headline figure does not need (none today: a plain "
+                        "run already does only setup, warmup, the timed "
+                        "steps and the result line)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
 
     have_gpu = torch.cuda.is_available()
     world_size = int(os.getenv("WORLD_SIZE", "1"))
@@ -135,11 +197,17 @@ def main():
     y = torch.randint(0, config.vocab_size, (args.batch, args.seq),
                       generator=g).to(device)
 
-    def step():
+    last = {}
+
+    def step(keep=False):
         wrapped.require_backward_grad_sync = True
-        _, loss = wrapped(x, y)
+        logits, loss = wrapped(x, y)
         loss.backward()
         optimizer.step()
+        if keep:
+            # only the last timed step holds on to its logits, so the
+            # steps before it free them exactly as a plain run does
+            last["logits"], last["loss"] = logits, loss
         return loss
 
     for _ in range(args.warmup):
@@ -153,8 +221,9 @@ def main():
         # candidate timing whose composite transients never recur
         torch.cuda.reset_peak_memory_stats()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    dump = args.dump_outputs is not None and rank == 0
+    for i in range(args.steps):
+        step(keep=dump and i == args.steps - 1)
     if have_gpu:
         torch.cuda.synchronize()
     if distributed:
@@ -166,6 +235,10 @@ def main():
                          if have_gpu else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if dump:
+        dump_outputs(args.dump_outputs, last["loss"], last["logits"],
+                     wrapped.named_parameters())
 
     n_gpus = world_size if have_gpu else args.gpus
     tokens_per_step = args.batch * args.seq * world_size

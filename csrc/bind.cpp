@@ -29,8 +29,9 @@ hipError_t tdsa_column_sum(const void*, float*, void*, int, int, int,
                            hipStream_t);
 hipError_t tdsa_embedding_fwd(const void*, const long long*, void*, long long,
                               int, int, hipStream_t);
-hipError_t tdsa_embedding_bwd(const void*, const long long*, float*, long long,
-                              int, long long, int, hipStream_t);
+hipError_t tdsa_embedding_bwd(const void*, const long long*, const long long*,
+                              float*, float*, long long, int, long long, int,
+                              hipStream_t);
 hipError_t tdsa_ce_fwd(const void*, const long long*, float*, float*, int*,
                        long long, int, long long, int, hipStream_t);
 hipError_t tdsa_ce_bwd(const void*, const long long*, const float*, void*,
@@ -217,9 +218,19 @@ at::Tensor embedding_bwd(at::Tensor dy, at::Tensor idx, int64_t num_embeddings,
   const int D = dy.size(-1);
   auto dw32 = at::zeros({num_embeddings, (long long)D},
                         dy.options().dtype(at::kFloat));
-  check_hip(tdsa_embedding_bwd(dy.data_ptr(), (const long long*)idx.data_ptr<int64_t>(),
-                               dw32.data_ptr<float>(), R, D, padding_idx,
-                               dtype_flag(dy), cur_stream()),
+  // stable sort: equal indices keep their dy-row order, so every table row
+  // is summed in one fixed order
+  auto sorted = at::sort(idx.reshape({-1}), /*stable=*/true, /*dim=*/0,
+                         /*descending=*/false);
+  auto sidx = std::get<0>(sorted).contiguous();
+  auto perm = std::get<1>(sorted).contiguous();
+  // scratch for the piece sums of indices that occur more than 32 times
+  auto part = at::empty({R, (long long)D}, dy.options().dtype(at::kFloat));
+  check_hip(tdsa_embedding_bwd(dy.data_ptr(), (const long long*)sidx.data_ptr<int64_t>(),
+                               (const long long*)perm.data_ptr<int64_t>(),
+                               dw32.data_ptr<float>(), part.data_ptr<float>(),
+                               R, D, padding_idx, dtype_flag(dy),
+                               cur_stream()),
             "embedding_bwd");
   return dw32;
 }
@@ -234,14 +245,15 @@ std::vector<at::Tensor> cross_entropy_fwd(at::Tensor logits, at::Tensor targets,
   const int V = logits.size(1);
   auto f32 = logits.options().dtype(at::kFloat);
   auto lse = at::empty({R}, f32);
-  auto loss_sum = at::zeros({}, f32);
+  // per-row losses, summed below in torch's fixed reduction order
+  auto row_loss = at::empty({R}, f32);
   auto n_valid32 = at::zeros({}, logits.options().dtype(at::kInt));
   check_hip(tdsa_ce_fwd(logits.data_ptr(), (const long long*)targets.data_ptr<int64_t>(),
-                        lse.data_ptr<float>(), loss_sum.data_ptr<float>(),
+                        lse.data_ptr<float>(), row_loss.data_ptr<float>(),
                         n_valid32.data_ptr<int>(), R, V, ignore_index,
                         dtype_flag(logits), cur_stream()),
             "cross_entropy_fwd");
-  return {loss_sum, lse, n_valid32.to(at::kLong)};
+  return {row_loss.sum(), lse, n_valid32.to(at::kLong)};
 }
 
 at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor targets,
@@ -414,11 +426,12 @@ at::Tensor gemm_tn(at::Tensor dy2, at::Tensor x2) {
   TORCH_CHECK(splits > 0, "gemm_tn: unsupported shape (need M%64==0, "
               "N%128==0, K%128==0), got ", M, "x", N, "/", K);
   auto f32 = dy2.options().dtype(at::kFloat);
-  auto dw32 = splits > 1 ? at::zeros({N, K}, f32) : at::empty({N, K}, f32);
+  // one [N, K] slab per M-split, summed here in slab order (deterministic)
+  auto dw32 = at::empty({(long long)splits, (long long)N, (long long)K}, f32);
   check_hip(tdsa_gemm_tn(dy2.data_ptr(), x2.data_ptr(),
                          dw32.data_ptr<float>(), M, N, K, cur_stream()),
             "gemm_tn");
-  return dw32.to(at::kBFloat16);
+  return (splits > 1 ? dw32.sum(0) : dw32.select(0, 0)).to(at::kBFloat16);
 }
 
 // ---- attention ------------------------------------------------------------

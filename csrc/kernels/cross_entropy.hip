@@ -40,12 +40,13 @@ template <> struct RowVec<bf16, 8> {
   static DEV_INLINE void store(bf16* p, V v) { store8(p, v); }
 };
 
-// One workgroup per row (grid-strided). Writes lse[row] (fp32) and
-// atomically accumulates loss_sum (fp32 scalar) and n_valid (int32).
+// One workgroup per row (grid-strided). Writes lse[row] and the row's loss
+// row_loss[row] (fp32, 0 for ignored rows; the caller sums them in a fixed
+// order) and atomically counts n_valid (int32, order-independent).
 template <typename T, int W>
 __global__ void ce_fwd_kernel(const T* __restrict__ logits,
                               const long long* __restrict__ targets,
-                              float* __restrict__ lse, float* __restrict__ loss_sum,
+                              float* __restrict__ lse, float* __restrict__ row_loss,
                               int* __restrict__ n_valid, long long R, int V,
                               long long ignore_index) {
   using RV = RowVec<T, W>;
@@ -55,10 +56,9 @@ __global__ void ce_fwd_kernel(const T* __restrict__ logits,
   const int lane = tid & (WAVE - 1);
   const int wid = tid / WAVE;
   const int nw = blockDim.x / WAVE;
-  // block-local loss/count accumulators: one atomicAdd per BLOCK at the end
-  // (a per-row atomicAdd on the single loss scalar serialized 32k blocks —
-  // measured 4x the kernel's HBM floor)
-  float loss_acc = 0.f;
+  // block-local count: one atomicAdd per BLOCK at the end (a per-row
+  // atomicAdd on a single scalar serialized 32k blocks — measured 4x the
+  // kernel's HBM floor)
   int valid_acc = 0;
   for (long long row = blockIdx.x; row < R; row += gridDim.x) {
     const T* lr = logits + row * V;
@@ -110,19 +110,17 @@ __global__ void ce_fwd_kernel(const T* __restrict__ logits,
         float l = mm + __logf(ss2);
         lse[row] = l;
         const long long t = targets[row];
+        float row_l = 0.f;
         if (t != ignore_index) {
-          float picked = (float)lr[t];
-          loss_acc += l - picked;
+          row_l = l - (float)lr[t];
           valid_acc += 1;
         }
+        row_loss[row] = row_l;
       }
     }
     __syncthreads();
   }
-  if (tid == 0 && valid_acc > 0) {
-    atomicAdd(loss_sum, loss_acc);
-    atomicAdd(n_valid, valid_acc);
-  }
+  if (tid == 0 && valid_acc > 0) atomicAdd(n_valid, valid_acc);
 }
 
 // dlogits = valid ? (exp(logit - lse) - onehot) * scale : 0
@@ -175,7 +173,7 @@ using namespace tdsa;
 extern "C" {
 
 hipError_t tdsa_ce_fwd(const void* logits, const long long* targets, float* lse,
-                       float* loss_sum, int* n_valid, long long R, int V,
+                       float* row_loss, int* n_valid, long long R, int V,
                        long long ignore_index, int is_bf16, hipStream_t stream) {
   const int block = 256;
   // Row bases logits+row*V must stay 16B-aligned for the vector loads:
@@ -187,11 +185,11 @@ hipError_t tdsa_ce_fwd(const void* logits, const long long* targets, float* lse,
   const int grid = (int)((R < cap) ? R : cap);
   if (is_bf16)
     hipLaunchKernelGGL((ce_fwd_kernel<bf16, 8>), dim3(grid), dim3(block), 0,
-                       stream, (const bf16*)logits, targets, lse, loss_sum,
+                       stream, (const bf16*)logits, targets, lse, row_loss,
                        n_valid, R, V, ignore_index);
   else
     hipLaunchKernelGGL((ce_fwd_kernel<float, 4>), dim3(grid), dim3(block), 0,
-                       stream, (const float*)logits, targets, lse, loss_sum,
+                       stream, (const float*)logits, targets, lse, row_loss,
                        n_valid, R, V, ignore_index);
   return hipGetLastError();
 }

@@ -18,9 +18,10 @@
 // LDS images (dy 64x128, x 64x128), with the next chunk's global loads
 // issued before the compute (fetch/put split — they fly under the MFMAs).
 // The output is tiny (N*K vs M*K inputs), so workgroups additionally
-// split the M reduction (grid.y) and combine 128x128 fp32 partials with
-// atomicAdd into a zeroed fp32 buffer (skipped when grid.y == 1); the
-// caller converts to bf16.
+// split the M reduction (grid.y); each split stores its 128x128 fp32
+// partials into its own [N, K] slab of a [splits, N, K] buffer, and the
+// caller sums the slabs in a fixed order and converts to bf16 (an fp32
+// atomicAdd combine gave run-to-run different sums at 3+ splits).
 //
 // Reference hot path being replaced:
 // /root/reference/tiny_deepspeed/core/module/ops/linear.py:59-68.
@@ -75,7 +76,7 @@ DEV_INLINE void tn_remap2(int gx, int gy, int& tile, int& split,
 // NW waves; output tile (NW*32) x 128. Wave w owns n-band [32w, 32w+32) x
 // 128 k. NW=8 halves the staged bytes per FLOP vs NW=4 (the dy slice is
 // amortized over twice the MFMA work) — used when N % 256 == 0.
-template <int NW, bool ATOMIC>
+template <int NW, bool SPLIT>
 __launch_bounds__(NW * WAVE)
 __global__ void gemm_tn_kernel(const bf16* __restrict__ dy,
                                const bf16* __restrict__ x,
@@ -163,17 +164,17 @@ __global__ void gemm_tn_kernel(const bf16* __restrict__ dy,
   }
 
   // epilogue: C[32x32] lane l reg r -> row crow(r,h32), col l%32
+  // SPLIT: this M-split's partial goes to its own [N, K] slab of the
+  // [splits, N, K] buffer; the caller adds the slabs in a fixed order
   const int col = k0 + (lane & 31);
+  if (SPLIT) dw += (long long)split * N * K;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const long long idx =
           (long long)(n0 + wave * 32 + crow(r, h32)) * K + col + dt * 32;
-      if (ATOMIC)
-        atomicAdd(dw + idx, acc[dt][r]);
-      else
-        dw[idx] = acc[dt][r];
+      dw[idx] = acc[dt][r];
     }
   }
 }
@@ -196,19 +197,27 @@ static int tn_nw(int N) {
   return nw;
 }
 
-// Returns the split count the launcher will use (for the caller to decide
-// whether the fp32 buffer needs zeroing); <=0 means shape unsupported.
+// Returns the split count the launcher will use (the caller sizes the fp32
+// buffer as [splits, N, K]); <=0 means shape unsupported.
 int tdsa_gemm_tn_splits(long long M, int N, int K) {
   if (M <= 0 || (M & 63) || (N & 127) || (K & 127)) return 0;
   const int nw = tn_nw(N);
   const long long tiles = (long long)(N / (nw * 32)) * (K >> 7);
   // ~512 total workgroups (2 per CU): the splits sweep measured 8 splits
   // at 64 tiles (512 wgs) 25% faster than 32 splits — more splits just
-  // multiply the fp32 atomic traffic once every CU has work
+  // multiply the fp32 partial traffic once every CU has work. (That sweep
+  // combined partials with atomicAdd; with one slab per split the heuristic
+  // is kept and each extra split costs one more [N, K] fp32 slab to store
+  // and sum.)
   long long want = (512 + tiles - 1) / tiles;
   long long maxs = M >> 6;  // at least one 64-chunk per split
   if (want > maxs) want = maxs;
   if (const char* v = getenv("TDSA_GEMM_TN_SPLITS")) want = atoll(v);
+  // the caller allocates splits * N * K fp32: cap the workspace at 1 GiB
+  // (heuristic shapes need at most 64 slabs of 128x128; this bounds the
+  // override)
+  const long long slab = (long long)N * K * 4;
+  if (want * slab > (1ll << 30)) want = (1ll << 30) / slab;
   if (want < 1) want = 1;
   return (int)want;
 }

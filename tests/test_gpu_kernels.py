@@ -351,7 +351,7 @@ def test_layernorm_wide_bwd_gpu(N, dtype):
 
 @pytest.mark.parametrize("M,N,K", [
     (64, 128, 128),        # single tile, single chunk
-    (4096, 1024, 1024),    # multi-split (atomic path)
+    (4096, 1024, 1024),    # multi-split (one slab per split)
     (2048, 3072, 1024),    # gpt2-medium c_attn family
     (8320, 1024, 4096),    # non-power-of-two M, wide K
 ])
@@ -365,6 +365,38 @@ def test_gemm_tn_gpu(M, N, K):
     assert dw.shape == (N, K) and dw.dtype == torch.bfloat16
     ref = torch.matmul(dy.t().float(), x.float())
     _close(dw, ref, 1e-2, f"gemm_tn {M}x{N}x{K}")
+
+
+def test_fixed_order_reductions_repeat_bitwise_gpu():
+    """The three reductions on the training path that once combined fp32
+    partials with atomicAdd (gemm_tn split-M, embedding backward, the
+    cross-entropy loss sum) add in a fixed order: the same inputs give the
+    same bits on every call. Shapes put many partials on each output (8
+    M-splits; ~128 rows per table row plus one run of 4096; 4096 row
+    losses), where a scheduling-order sum differs between calls."""
+    import importlib
+    # the package re-exports functions under the modules' own names
+    ce = importlib.import_module("tiny_deepspeed_amd.ops.cross_entropy")
+    emb = importlib.import_module("tiny_deepspeed_amd.ops.embedding")
+    torch.manual_seed(0)
+    ext = _ext.get_ext()
+    dy = torch.randn(4096, 1024, device="cuda", dtype=torch.bfloat16) * 0.05
+    x = torch.randn(4096, 1024, device="cuda", dtype=torch.bfloat16)
+    dw0 = ext.gemm_tn(dy, x)
+    idx = torch.randint(0, 64, (8192,), device="cuda")
+    idx[1000:5096] = 7                      # one long run of equal indices
+    g = torch.randn(8192, 256, device="cuda", dtype=torch.bfloat16)
+    de0 = emb.emb_bwd_hip(idx, g, 64, None)
+    ref = torch.zeros(64, 256, dtype=torch.float64, device="cuda")
+    ref.index_add_(0, idx, g.double())
+    _close(de0, ref, 1e-2, "emb bwd skewed")
+    logits = torch.randn(4096, 1024, device="cuda", dtype=torch.bfloat16) * 3
+    tgt = torch.randint(0, 1024, (4096,), device="cuda")
+    l0 = ce.ce_fwd_hip(logits, tgt, -100)[0]
+    for _ in range(3):
+        assert torch.equal(ext.gemm_tn(dy, x), dw0)
+        assert torch.equal(emb.emb_bwd_hip(idx, g, 64, None), de0)
+        assert torch.equal(ce.ce_fwd_hip(logits, tgt, -100)[0], l0)
 
 
 def test_gemm_tn_via_linear_weight_grad_gpu():

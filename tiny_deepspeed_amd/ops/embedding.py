@@ -5,9 +5,9 @@ Capability parity with
 candidate-list dispatch like the reference (``ops/linear.py:9-17``).
 
 MI355X design: forward is a vectorized row-gather HIP kernel; the weight
-grad is an atomic scatter-add into an fp32 accumulation buffer (bf16 grads
-would lose counts and bf16 atomics are slow), converted to the param dtype
-at the end. padding_idx rows are skipped in the grad like torch.
+grad sums each table row's contributions in fp32 in sorted-index order, in
+pieces of at most 32 rows that a second kernel joins (no atomics, so it is
+identical from run to run), converted to the param dtype at the end. padding_idx rows are skipped in the grad like torch.
 """
 
 import torch
