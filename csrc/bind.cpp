@@ -16,11 +16,12 @@ extern "C" {
 hipError_t tdsa_ln_fwd(const void*, const void*, void*, const void*,
                        const void*, void*, float*, float*, int, int, float,
                        int, hipStream_t);
-int tdsa_ln_bwd_dx_stripes(int M);
+int tdsa_ln_bwd_dx_stripes(int M, int N, int is_bf16);
+void tdsa_ln_rowwave_info(int, int, int, int*, int*, int*, int*);
 hipError_t tdsa_ln_bwd_dx(const void*, const void*, const void*, const void*,
                           const float*, const float*, void*, float*, float*,
                           int, int, int, hipStream_t);
-hipError_t tdsa_ln_bwd_dwdb(const float*, const float*, float*, float*, int,
+hipError_t tdsa_ln_bwd_dwdb(const float*, const float*, void*, void*, int, int,
                             int, hipStream_t);
 hipError_t tdsa_gelu_fwd(const void*, void*, long long, int, hipStream_t);
 hipError_t tdsa_gelu_bwd(const void*, const void*, void*, long long, int,
@@ -129,7 +130,7 @@ std::vector<at::Tensor> layernorm_bwd_dx(at::Tensor dy, at::Tensor x,
   (void)n_stripes;  // stripe count is chosen device-side for full occupancy
   const int N = x.size(-1);
   const long long M = x.numel() / N;
-  const int G = tdsa_ln_bwd_dx_stripes((int)M);
+  const int G = tdsa_ln_bwd_dx_stripes((int)M, N, dtype_flag(x));
   auto dx = at::empty_like(x);
   auto f32 = x.options().dtype(at::kFloat);
   auto pdw = at::empty({G, N}, f32);
@@ -151,17 +152,34 @@ std::vector<at::Tensor> layernorm_bwd_dx(at::Tensor dy, at::Tensor x,
   return {dx, pdw, pdb};
 }
 
-std::vector<at::Tensor> layernorm_bwd_dwdb(at::Tensor pdw, at::Tensor pdb) {
+// dtype: output dtype of dw/db (float32 or bfloat16, rounded in-kernel from
+// the fp32 sums); fp32 when absent.
+std::vector<at::Tensor> layernorm_bwd_dwdb(
+    at::Tensor pdw, at::Tensor pdb, c10::optional<at::ScalarType> dtype) {
   CHECK_IN(pdw); CHECK_IN(pdb);
+  const at::ScalarType out = dtype.value_or(at::kFloat);
+  TORCH_CHECK(out == at::kFloat || out == at::kBFloat16,
+              "layernorm_bwd_dwdb: dtype must be float32 or bfloat16");
   const int G = pdw.size(0);
   const int N = pdw.size(1);
-  auto dw = at::empty({N}, pdw.options());
-  auto db = at::empty({N}, pdb.options());
+  auto dw = at::empty({N}, pdw.options().dtype(out));
+  auto db = at::empty({N}, pdb.options().dtype(out));
   check_hip(tdsa_ln_bwd_dwdb(pdw.data_ptr<float>(), pdb.data_ptr<float>(),
-                             dw.data_ptr<float>(), db.data_ptr<float>(), G, N,
-                             cur_stream()),
+                             dw.data_ptr(), db.data_ptr(), G, N,
+                             out == at::kBFloat16, cur_stream()),
             "layernorm_bwd_dwdb");
   return {dw, db};
+}
+
+// Launch geometry of the row-per-wave LayerNorm path for an (M, N) problem:
+// (stripe count = backward waves, forward waves, forward batch depth,
+// backward batch depth, last routed bf16 N). Waves and depths are 0 when the
+// shape stays on the workgroup-per-row kernels (the stripe count never is).
+std::vector<int64_t> layernorm_rowwave_geometry(int64_t M, int64_t N,
+                                                bool is_bf16) {
+  int fw = 0, fd = 0, bd = 0, bound = 0;
+  tdsa_ln_rowwave_info((int)M, (int)N, is_bf16, &fw, &fd, &bd, &bound);
+  return {tdsa_ln_bwd_dx_stripes((int)M, (int)N, is_bf16), fw, fd, bd, bound};
 }
 
 // ---- elementwise ----------------------------------------------------------
@@ -559,7 +577,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("layernorm_bwd_dx", &layernorm_bwd_dx, py::arg("dy"), py::arg("x"),
           py::arg("w"), py::arg("mean"), py::arg("rstd"),
           py::arg("n_stripes"), py::arg("dh") = py::none());
-  mod.def("layernorm_bwd_dwdb", &layernorm_bwd_dwdb);
+  mod.def("layernorm_bwd_dwdb", &layernorm_bwd_dwdb, py::arg("pdw"),
+          py::arg("pdb"), py::arg("dtype") = py::none());
+  mod.def("layernorm_rowwave_geometry", &layernorm_rowwave_geometry,
+          py::arg("M"), py::arg("N"), py::arg("is_bf16") = true);
   mod.def("gelu_fwd", &gelu_fwd);
   mod.def("gelu_bwd", &gelu_bwd);
   mod.def("column_sum", &column_sum);

@@ -122,10 +122,12 @@ def layernorm_dwdb(workspace, dtype=None, tuner=None):
         pdw, pdb = workspace
         if _ext.use_native(pdw):
             ext = _ext.get_ext()
+            if dtype in (None, torch.float32, torch.bfloat16):
+                # the reduce kernel writes the parameter dtype itself
+                dw, db = ext.layernorm_bwd_dwdb(pdw, pdb, dtype)
+                return dw, db
             dw, db = ext.layernorm_bwd_dwdb(pdw, pdb)
-            if dtype is not None:
-                dw, db = dw.to(dtype), db.to(dtype)
-            return dw, db
+            return dw.to(dtype), db.to(dtype)
         dw = pdw.sum(dim=0)
         db = pdb.sum(dim=0)
     else:  # torch dx path: recompute from saved tensors
