@@ -11,16 +11,34 @@
 
 namespace tdsa {
 
-// merge two (m, s) logsumexp states (raw v_exp: exp(-inf) == 0, and the
-// branchless form keeps both scales well-defined for m == m2 == -inf)
-DEV_INLINE void lse_merge(float& m, float& s, float m2, float s2) {
-  float mn = fmaxf(m, m2);
-  float a = (m == -INFINITY) ? 0.f
-            : __builtin_amdgcn_exp2f(1.4426950408889634f * (m - mn));
-  float b = (m2 == -INFINITY) ? 0.f
-            : __builtin_amdgcn_exp2f(1.4426950408889634f * (m2 - mn));
-  s = s * a + s2 * b;
+// Scales a, b that bring two logsumexp states with maxima m, m2 to their
+// common maximum, which replaces m (raw v_exp: exp(-inf) == 0, and the
+// branchless form keeps both scales well-defined for m == m2 == -inf).
+DEV_INLINE void lse_scales(float& m, float m2, float& a, float& b) {
+  const float mn = fmaxf(m, m2);
+  a = (m == -INFINITY) ? 0.f
+      : __builtin_amdgcn_exp2f(1.4426950408889634f * (m - mn));
+  b = (m2 == -INFINITY) ? 0.f
+      : __builtin_amdgcn_exp2f(1.4426950408889634f * (m2 - mn));
   m = mn;
+}
+
+// merge two (m, s) logsumexp states
+DEV_INLINE void lse_merge(float& m, float& s, float m2, float s2) {
+  float a, b;
+  lse_scales(m, m2, a, b);
+  s = s * a + s2 * b;
+}
+
+// The same merge for the per-chunk loop, with both products rounded before
+// the add. Left to the optimizer, whether s*a + s2*b becomes an FMA depends
+// on the code around it, so lse would move in the last bit with an
+// unrelated edit of the loop; here the form is fixed.
+DEV_INLINE void lse_merge_chunk(float& m, float& s, float m2, float s2) {
+#pragma clang fp contract(off)
+  float a, b;
+  lse_scales(m, m2, a, b);
+  s = s * a + s2 * b;
 }
 
 template <typename T, int W>
@@ -71,12 +89,17 @@ __global__ void ce_fwd_kernel(const T* __restrict__ logits,
       float cm = RV::get(v, 0);
 #pragma unroll
       for (int k = 1; k < W; ++k) cm = fmaxf(cm, RV::get(v, k));
+      // a chunk that is all -inf (masked vocabulary padding) must contribute
+      // (-inf, 0): subtracting its own max would give -inf - -inf = NaN.
+      // One select per chunk, on the subtrahend only: every element then
+      // gives exp2(-inf) = 0, and any other chunk subtracts cm as before.
+      const float sub = (cm == -INFINITY) ? 0.f : cm;
       float cs = 0.f;
 #pragma unroll
       for (int k = 0; k < W; ++k)
         cs += __builtin_amdgcn_exp2f(1.4426950408889634f
-                                     * (RV::get(v, k) - cm));
-      lse_merge(m, s, cm, cs);
+                                     * (RV::get(v, k) - sub));
+      lse_merge_chunk(m, s, cm, cs);
     }
     const int rem0 = (V / W) * W;
     for (int j = rem0 + tid; j < V; j += blockDim.x) {
