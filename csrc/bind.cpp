@@ -124,10 +124,9 @@ std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, at::Tensor b,
 
 std::vector<at::Tensor> layernorm_bwd_dx(at::Tensor dy, at::Tensor x,
                                          at::Tensor w, at::Tensor mean,
-                                         at::Tensor rstd, int64_t n_stripes,
+                                         at::Tensor rstd,
                                          c10::optional<at::Tensor> dh) {
   CHECK_IN(dy); CHECK_IN(x); CHECK_IN(w);
-  (void)n_stripes;  // stripe count is chosen device-side for full occupancy
   const int N = x.size(-1);
   const long long M = x.numel() / N;
   const int G = tdsa_ln_bwd_dx_stripes((int)M, N, dtype_flag(x));
@@ -576,7 +575,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("b"), py::arg("eps"), py::arg("res") = py::none());
   mod.def("layernorm_bwd_dx", &layernorm_bwd_dx, py::arg("dy"), py::arg("x"),
           py::arg("w"), py::arg("mean"), py::arg("rstd"),
-          py::arg("n_stripes"), py::arg("dh") = py::none());
+          py::arg("dh") = py::none());
   mod.def("layernorm_bwd_dwdb", &layernorm_bwd_dwdb, py::arg("pdw"),
           py::arg("pdb"), py::arg("dtype") = py::none());
   mod.def("layernorm_rowwave_geometry", &layernorm_rowwave_geometry,

@@ -10,6 +10,8 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 
+#include <cstdlib>
+
 #define WAVE 64
 #define DEV_INLINE __device__ __forceinline__
 
@@ -111,12 +113,19 @@ DEV_INLINE float block_max(float v, float* scratch) {
     }                                                                      \
   } while (0)
 
-// Grid sizing for memory-bound grid-stride kernels (Guideline 11):
-// cap at ~8 blocks per CU and stride the rest.
+// Integer launch knob from the environment: `dflt` when unset, otherwise
+// atoll() of the value, whatever it holds.
+inline long long env_int(const char* name, long long dflt) {
+  const char* v = getenv(name);
+  return v ? atoll(v) : dflt;
+}
+
 DEV_INLINE int global_tid() { return blockIdx.x * blockDim.x + threadIdx.x; }
 DEV_INLINE int global_nthreads() { return gridDim.x * blockDim.x; }
 
-inline int ln_grid(long long work, int block) {
+// Grid sizing for memory-bound grid-stride kernels (Guideline 11):
+// cap at ~8 blocks per CU and stride the rest.
+inline int capped_grid(long long work, int block) {
   long long g = (work + block - 1) / block;
   const long long cap = 2048;
   if (g > cap) g = cap;

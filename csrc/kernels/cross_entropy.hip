@@ -7,8 +7,6 @@
 // pass writing (softmax - onehot) * scale. fp32 accumulation throughout.
 #include "common.h"
 
-#include <cstdlib>
-
 namespace tdsa {
 
 // Scales a, b that bring two logsumexp states with maxima m, m2 to their
@@ -203,8 +201,7 @@ hipError_t tdsa_ce_fwd(const void* logits, const long long* targets, float* lse,
   // reject V % W != 0 (mirrors the layernorm launcher guard; the python op
   // routes such shapes to the composite path instead).
   if (V % (is_bf16 ? 8 : 4)) return hipErrorInvalidValue;
-  long long cap = 32768;
-  if (const char* v = getenv("TDSA_CE_GRID")) cap = atoll(v);
+  const long long cap = env_int("TDSA_CE_GRID", 32768);
   const int grid = (int)((R < cap) ? R : cap);
   if (is_bf16)
     hipLaunchKernelGGL((ce_fwd_kernel<bf16, 8>), dim3(grid), dim3(block), 0,
@@ -223,8 +220,7 @@ hipError_t tdsa_ce_bwd(const void* logits, const long long* targets,
                        hipStream_t stream) {
   const int block = 256;
   if (V % (is_bf16 ? 8 : 4)) return hipErrorInvalidValue;  // see tdsa_ce_fwd
-  long long cap = 32768;
-  if (const char* v = getenv("TDSA_CE_GRID")) cap = atoll(v);
+  const long long cap = env_int("TDSA_CE_GRID", 32768);
   const int grid = (int)((R < cap) ? R : cap);
   if (is_bf16)
     hipLaunchKernelGGL((ce_bwd_kernel<bf16, 8>), dim3(grid), dim3(block), 0,

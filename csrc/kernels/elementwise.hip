@@ -131,7 +131,7 @@ hipError_t tdsa_gelu_fwd(const void* x, void* y, long long n, int is_bf16,
   if (is_bf16) {
     long long n8 = n / 8;
     if (n8)
-      hipLaunchKernelGGL(gelu_fwd_bf16, dim3(ln_grid(n8, block)), dim3(block), 0,
+      hipLaunchKernelGGL(gelu_fwd_bf16, dim3(capped_grid(n8, block)), dim3(block), 0,
                          stream, (const bf16*)x, (bf16*)y, n8);
     if (n % 8)
       hipLaunchKernelGGL(gelu_tail_bf16, dim3(1), dim3(8), 0, stream,
@@ -139,7 +139,7 @@ hipError_t tdsa_gelu_fwd(const void* x, void* y, long long n, int is_bf16,
   } else {
     long long n4 = n / 4;
     if (n4)
-      hipLaunchKernelGGL(gelu_fwd_f32, dim3(ln_grid(n4, block)), dim3(block), 0,
+      hipLaunchKernelGGL(gelu_fwd_f32, dim3(capped_grid(n4, block)), dim3(block), 0,
                          stream, (const float*)x, (float*)y, n4);
     if (n % 4)
       hipLaunchKernelGGL(gelu_tail_f32, dim3(1), dim3(4), 0, stream,
@@ -154,7 +154,7 @@ hipError_t tdsa_gelu_bwd(const void* dy, const void* x, void* dx, long long n,
   if (is_bf16) {
     long long n8 = n / 8;
     if (n8)
-      hipLaunchKernelGGL(gelu_bwd_bf16, dim3(ln_grid(n8, block)), dim3(block), 0,
+      hipLaunchKernelGGL(gelu_bwd_bf16, dim3(capped_grid(n8, block)), dim3(block), 0,
                          stream, (const bf16*)dy, (const bf16*)x, (bf16*)dx, n8);
     if (n % 8)
       hipLaunchKernelGGL(gelu_bwd_tail_bf16, dim3(1), dim3(8), 0, stream,
@@ -162,7 +162,7 @@ hipError_t tdsa_gelu_bwd(const void* dy, const void* x, void* dx, long long n,
   } else {
     long long n4 = n / 4;
     if (n4)
-      hipLaunchKernelGGL(gelu_bwd_f32, dim3(ln_grid(n4, block)), dim3(block), 0,
+      hipLaunchKernelGGL(gelu_bwd_f32, dim3(capped_grid(n4, block)), dim3(block), 0,
                          stream, (const float*)dy, (const float*)x, (float*)dx, n4);
     if (n % 4)
       hipLaunchKernelGGL(gelu_bwd_tail_f32, dim3(1), dim3(4), 0, stream,
@@ -184,12 +184,12 @@ hipError_t tdsa_column_sum(const void* dy, float* out32, void* out, int M, int N
   if (is_bf16) {
     hipLaunchKernelGGL(colsum_kernel<bf16>, grid, dim3(block), 0, stream,
                        (const bf16*)dy, out32, M, N, rows_per_chunk);
-    hipLaunchKernelGGL(cast_from_f32<bf16>, dim3(ln_grid(N, block)), dim3(block),
+    hipLaunchKernelGGL(cast_from_f32<bf16>, dim3(capped_grid(N, block)), dim3(block),
                        0, stream, out32, (bf16*)out, (long long)N);
   } else {
     hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(block), 0, stream,
                        (const float*)dy, out32, M, N, rows_per_chunk);
-    hipLaunchKernelGGL(cast_from_f32<float>, dim3(ln_grid(N, block)), dim3(block),
+    hipLaunchKernelGGL(cast_from_f32<float>, dim3(capped_grid(N, block)), dim3(block),
                        0, stream, out32, (float*)out, (long long)N);
   }
   return hipGetLastError();

@@ -121,20 +121,20 @@ hipError_t tdsa_embedding_fwd(const void* weight, const long long* idx, void* ou
   const int block = 256;
   if (is_bf16 && D % 8 == 0) {
     long long work = R * (D / 8);
-    hipLaunchKernelGGL((emb_fwd_vec<bf16, 8>), dim3(ln_grid(work, block)),
+    hipLaunchKernelGGL((emb_fwd_vec<bf16, 8>), dim3(capped_grid(work, block)),
                        dim3(block), 0, stream, (const bf16*)weight, idx,
                        (bf16*)out, R, D);
   } else if (!is_bf16 && D % 4 == 0) {
     long long work = R * (D / 4);
-    hipLaunchKernelGGL((emb_fwd_vec<float, 4>), dim3(ln_grid(work, block)),
+    hipLaunchKernelGGL((emb_fwd_vec<float, 4>), dim3(capped_grid(work, block)),
                        dim3(block), 0, stream, (const float*)weight, idx,
                        (float*)out, R, D);
   } else if (is_bf16) {
-    hipLaunchKernelGGL(emb_fwd_scalar<bf16>, dim3(ln_grid(R * D, block)),
+    hipLaunchKernelGGL(emb_fwd_scalar<bf16>, dim3(capped_grid(R * D, block)),
                        dim3(block), 0, stream, (const bf16*)weight, idx,
                        (bf16*)out, R, D);
   } else {
-    hipLaunchKernelGGL(emb_fwd_scalar<float>, dim3(ln_grid(R * D, block)),
+    hipLaunchKernelGGL(emb_fwd_scalar<float>, dim3(capped_grid(R * D, block)),
                        dim3(block), 0, stream, (const float*)weight, idx,
                        (float*)out, R, D);
   }
@@ -150,16 +150,16 @@ hipError_t tdsa_embedding_bwd(const void* dy, const long long* idx,
                               int is_bf16, hipStream_t stream) {
   const int block = 256;
   if (is_bf16)
-    hipLaunchKernelGGL(emb_bwd_kernel<bf16>, dim3(ln_grid(R * D, block)),
+    hipLaunchKernelGGL(emb_bwd_kernel<bf16>, dim3(capped_grid(R * D, block)),
                        dim3(block), 0, stream, (const bf16*)dy, idx, perm, dw32,
                        part, R, D, padding_idx);
   else
-    hipLaunchKernelGGL(emb_bwd_kernel<float>, dim3(ln_grid(R * D, block)),
+    hipLaunchKernelGGL(emb_bwd_kernel<float>, dim3(capped_grid(R * D, block)),
                        dim3(block), 0, stream, (const float*)dy, idx, perm, dw32,
                        part, R, D, padding_idx);
   if (R > EMB_PIECE)
     hipLaunchKernelGGL(emb_bwd_join,
-                       dim3(ln_grid(((R - 1) / EMB_PIECE) * D, block)),
+                       dim3(capped_grid(((R - 1) / EMB_PIECE) * D, block)),
                        dim3(block), 0, stream, idx, part, dw32, R, D,
                        padding_idx);
   return hipGetLastError();

@@ -10,7 +10,7 @@
 // the workgroup-per-row and wide kernels.
 #include "common.h"
 
-#include <cstdlib>
+#include <type_traits>
 
 namespace tdsa {
 
@@ -33,13 +33,22 @@ template <> struct VecTraits<bf16> {
 };
 
 // ---- workgroup-per-row kernels (fp32, and bf16 with TDSA_LN_ROWWAVE=0) ------
+// Register-cache depth: a thread keeps up to LN_WG_MAXITER vectors of its row
+// between the statistics pass and the apply pass. The kernels' MAXITER
+// argument and the launchers' wide-row test both take it from here; a row
+// with more than LN_WG_MAXITER * blockDim.x vectors would index past the
+// cache.
+constexpr int LN_WG_MAXITER = 2;
+
 // HAS_RES: fused residual add — h = x + res is computed in-kernel, written
 // out (the residual stream) and normalized, saving the separate elementwise
 // add pass + launch per LayerNorm site (2 per transformer block).
-// ONE_WAVE: 64-thread blocks, one wave per row — the two per-row reductions
-// become pure wave shuffles with NO __syncthreads / LDS at all (needs a
-// deeper register cache: MAXITER up to 4 covers N<=2048 bf16 / 1024 fp32).
-template <typename T, bool HAS_RES, int MAXITER = 2, bool ONE_WAVE = false>
+// MAXITER = 0 is the wide-row form: nothing is cached and the apply pass
+// reads the row a second time (L2-resident at practical widths), so any N
+// fits.
+// There is no one-wave-per-workgroup form: at one row per 64-thread
+// workgroup it measured 2-3x slower (docs/kernels.md).
+template <typename T, bool HAS_RES, int MAXITER>
 __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
                               T* __restrict__ h, const T* __restrict__ w,
                               const T* __restrict__ b, T* __restrict__ y,
@@ -47,6 +56,7 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res
                               int M, int N, float eps) {
   using VT = VecTraits<T>;
   constexpr int W = VT::W;
+  constexpr bool CACHED = MAXITER > 0;
   __shared__ float scratch[2 * 1024 / WAVE];
   const int tid = threadIdx.x;
   const int nth = blockDim.x;
@@ -54,7 +64,7 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res
     const T* xr = x + (long long)row * N;
     const T* rr = HAS_RES ? res + (long long)row * N : nullptr;
     T* hr = HAS_RES ? h + (long long)row * N : nullptr;
-    typename VT::V xc[MAXITER];
+    typename VT::V xc[CACHED ? MAXITER : 1];
     float s = 0.f, ss = 0.f;
     {
       int it = 0;
@@ -69,7 +79,7 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res
           VT::store(hr + i, hv);
           v = hv;
         }
-        xc[it] = v;
+        if (CACHED) xc[it] = v;
 #pragma unroll
         for (int k = 0; k < W; ++k) {
           float f = VT::get(v, k);
@@ -78,12 +88,7 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res
         }
       }
     }
-    if (ONE_WAVE) {
-      s = wave_sum(s);
-      ss = wave_sum(ss);
-    } else {
-      block_sum2(s, ss, scratch);
-    }
+    block_sum2(s, ss, scratch);
     const float mu = s / N;
     const float var = fmaxf(ss / N - mu * mu, 0.0f);
     const float rs = rsqrtf(var + eps);
@@ -91,11 +96,13 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res
       mean[row] = mu;
       rstd[row] = rs;
     }
+    // uncached: re-read the (already residual-fused) row
+    const T* src = HAS_RES ? hr : xr;
     T* yr = y + (long long)row * N;
     {
       int it = 0;
       for (int i = tid * W; i < N; i += nth * W, ++it) {
-        typename VT::V xv = xc[it];
+        typename VT::V xv = CACHED ? xc[it] : VT::load(src + i);
         typename VT::V wv = VT::load(w + i);
         typename VT::V bv = VT::load(b + i);
         typename VT::V ov;
@@ -110,37 +117,24 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res
   }
 }
 
-// Backward dx (+ optionally the dw/db stripe partials). Grid = G blocks;
-// block g handles rows g, g+G, ...; with STRIPES it accumulates dw/db into
-// pdw[g*N..] (no atomics).
-// Measured split (r2): the fused form chains rows with two block-wide
-// reduction barriers each, capping dx at ~2.1 TB/s while the fwd kernel
-// reaches 3.1. The launcher now runs dx at FULL grid (one row per block,
-// STRIPES=false) and a separate barrier-free streaming kernel
-// (ln_dwdb_accum_kernel) produces the stripes — one extra dy/x read buys
-// unchained dx rows.
+// Backward dx, launched at one row per workgroup; the dw/db stripes come from
+// ln_dwdb_accum_kernel below. A fused form that also accumulated the stripes
+// here chained a workgroup's rows through two block-wide reduction barriers
+// each and measured 9 % slower than the pair, although the pair reads dy and
+// x once more (docs/kernels.md).
 // HAS_DH: dx += dh (gradient of the residual-stream output h), fusing the
 // backward-side elementwise add of the residual connection.
-template <typename T, int MAXITER, bool HAS_DH, bool STRIPES = true,
-          bool ONE_WAVE = false>
+template <typename T, int MAXITER, bool HAS_DH>
 __global__ void ln_bwd_dx_kernel(const T* __restrict__ dy, const T* __restrict__ dh,
                                  const T* __restrict__ x,
                                  const T* __restrict__ w, const float* __restrict__ mean,
                                  const float* __restrict__ rstd, T* __restrict__ dx,
-                                 float* __restrict__ pdw, float* __restrict__ pdb,
                                  int M, int N) {
   using VT = VecTraits<T>;
   constexpr int W = VT::W;
   __shared__ float scratch[2 * 1024 / WAVE];
   const int tid = threadIdx.x;
   const int nth = blockDim.x;
-  float accdw[MAXITER][W];
-  float accdb[MAXITER][W];
-#pragma unroll
-  for (int it = 0; it < MAXITER; ++it)
-#pragma unroll
-    for (int k = 0; k < W; ++k) accdw[it][k] = accdb[it][k] = 0.f;
-
   for (int row = blockIdx.x; row < M; row += gridDim.x) {
     const T* dyr = dy + (long long)row * N;
     const T* xr = x + (long long)row * N;
@@ -163,19 +157,10 @@ __global__ void ln_bwd_dx_kernel(const T* __restrict__ dy, const T* __restrict__
           float wdy = VT::get(wv, k) * d;
           c1 += xh * wdy;
           c2 += wdy;
-          if (STRIPES) {
-            accdw[it][k] += d * xh;
-            accdb[it][k] += d;
-          }
         }
       }
     }
-    if (ONE_WAVE) {
-      c1 = wave_sum(c1);
-      c2 = wave_sum(c2);
-    } else {
-      block_sum2(c1, c2, scratch);
-    }
+    block_sum2(c1, c2, scratch);
     c1 /= N;
     c2 /= N;
     T* dxr = dx + (long long)row * N;
@@ -202,25 +187,12 @@ __global__ void ln_bwd_dx_kernel(const T* __restrict__ dy, const T* __restrict__
       }
     }
   }
-  // stripe write: block-owned rows of pdw/pdb
-  if (STRIPES) {
-    float* sdw = pdw + (long long)blockIdx.x * N;
-    float* sdb = pdb + (long long)blockIdx.x * N;
-    int it = 0;
-    for (int i = tid * W; i < N; i += nth * W, ++it) {
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        sdw[i + k] = accdw[it][k];
-        sdb[i + k] = accdb[it][k];
-      }
-    }
-  }
 }
 
 // Streaming dw/db stripe accumulation (no barriers: the per-column sums
-// need no cross-thread reduction). Block g chains rows g, g+G, ... exactly
-// like the fused form, but with nothing serializing the row loop it runs
-// at the HBM read floor.
+// need no cross-thread reduction). Block g chains rows g, g+G, ... into
+// stripe row g of pdw/pdb (no atomics); with nothing serializing the row
+// loop it runs at the HBM read floor.
 template <typename T, int MAXITER>
 __global__ void ln_dwdb_accum_kernel(const T* __restrict__ dy,
                                      const T* __restrict__ x,
@@ -276,9 +248,9 @@ __global__ void ln_dwdb_accum_kernel(const T* __restrict__ dy,
 // Memory-level parallelism is explicit instead of left to however many
 // tiny workgroups a CU holds: a wave issues every global load of a batch of
 // R rows before the first reduction of that batch, and several such waves
-// share a SIMD. (The earlier 64-thread one-wave attempt behind TDSA_LN_WAVE
-// had one row per workgroup, 32768 tiny workgroups and one row of loads in
-// flight per wave; that, not the missing barrier, made it slow.)
+// share a SIMD. (An earlier one-wave attempt with one row per 64-thread
+// workgroup had 32768 tiny workgroups and one row of loads in flight per
+// wave; that, not the missing barrier, made it 2-3x slower.)
 #define LN_RW_BLOCK 256
 #define LN_RW_WAVES (LN_RW_BLOCK / WAVE)
 #define LN_RW_MAXVEC 4
@@ -538,76 +510,13 @@ __global__ __launch_bounds__(LN_RW_BLOCK) void ln_bwd_rowwave_kernel(
   }
 }
 
-// ---- wide-row fallback ----------------------------------------------------
-// Rows beyond the register-cache bound (N > 2*block*W) use a two-pass
-// grid-strided form that re-reads the row from global (L2-resident at
-// practical widths). Correctness fallback for non-GPT widths — the narrow
-// register-cached kernels above stay the hot path (VERDICT r1 weak #6:
-// the old launcher returned hipErrorInvalidValue past N=4096 bf16).
-template <typename T, bool HAS_RES>
-__global__ void ln_fwd_wide_kernel(const T* __restrict__ x,
-                                   const T* __restrict__ res, T* __restrict__ h,
-                                   const T* __restrict__ w, const T* __restrict__ b,
-                                   T* __restrict__ y, float* __restrict__ mean,
-                                   float* __restrict__ rstd, int M, int N,
-                                   float eps) {
-  using VT = VecTraits<T>;
-  constexpr int W = VT::W;
-  __shared__ float scratch[2 * 1024 / WAVE];
-  const int tid = threadIdx.x;
-  const int nth = blockDim.x;
-  for (int row = blockIdx.x; row < M; row += gridDim.x) {
-    const T* xr = x + (long long)row * N;
-    const T* rr = HAS_RES ? res + (long long)row * N : nullptr;
-    T* hr = HAS_RES ? h + (long long)row * N : nullptr;
-    float s = 0.f, ss = 0.f;
-    for (int i = tid * W; i < N; i += nth * W) {
-      typename VT::V v = VT::load(xr + i);
-      if (HAS_RES) {
-        typename VT::V rv = VT::load(rr + i);
-        typename VT::V hv;
-#pragma unroll
-        for (int k = 0; k < W; ++k)
-          VT::set(hv, k, VT::get(v, k) + VT::get(rv, k));
-        VT::store(hr + i, hv);
-        v = hv;
-      }
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        float f = VT::get(v, k);
-        s += f;
-        ss += f * f;
-      }
-    }
-    block_sum2(s, ss, scratch);
-    const float mu = s / N;
-    const float var = fmaxf(ss / N - mu * mu, 0.0f);
-    const float rs = rsqrtf(var + eps);
-    if (tid == 0) {
-      mean[row] = mu;
-      rstd[row] = rs;
-    }
-    // pass 2: re-read the (already residual-fused) row
-    const T* src = HAS_RES ? hr : xr;
-    T* yr = y + (long long)row * N;
-    for (int i = tid * W; i < N; i += nth * W) {
-      typename VT::V xv = VT::load(src + i);
-      typename VT::V wv = VT::load(w + i);
-      typename VT::V bv = VT::load(b + i);
-      typename VT::V ov;
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        float xh = (VT::get(xv, k) - mu) * rs;
-        VT::set(ov, k, xh * VT::get(wv, k) + VT::get(bv, k));
-      }
-      VT::store(yr + i, ov);
-    }
-  }
-}
-
-// Wide backward: stripe partials accumulate straight into the block-owned
-// global stripe rows (read-modify-write, no atomics needed) after a
-// zero-init sweep — registers cannot hold a whole wide row.
+// ---- wide-row backward -----------------------------------------------------
+// Rows beyond the register-cache bound (N > LN_WG_MAXITER * block * W) are a
+// correctness fallback for non-GPT widths; the forward is ln_fwd_kernel with
+// MAXITER = 0. Both passes read dy and x from global (L2-resident at
+// practical widths), and the stripe partials accumulate straight into the
+// block-owned global stripe rows (read-modify-write, no atomics needed)
+// after a zero-init sweep — registers cannot hold a whole wide row.
 template <typename T, bool HAS_DH>
 __global__ void ln_bwd_dx_wide_kernel(const T* __restrict__ dy,
                                       const T* __restrict__ dh,
@@ -737,14 +646,12 @@ __global__ __launch_bounds__(LN_DWDB_BLOCK) void ln_bwd_dwdb_kernel(
 
 using namespace tdsa;
 
-extern "C" {
-
+// ---- launch geometry --------------------------------------------------------
 // Row-per-wave routing: bf16, N % 8 == 0, at most LN_RW_MAXVEC 16-byte
 // vectors per lane (N <= 2048). TDSA_LN_ROWWAVE=0 gives the workgroup-per-row
 // path back. Returns the vectors per lane, or 0 when the shape is not routed.
 static int ln_rw_nvec(int N, int is_bf16) {
-  int on = 1;
-  if (const char* v = getenv("TDSA_LN_ROWWAVE")) on = atoi(v);
+  const int on = (int)env_int("TDSA_LN_ROWWAVE", 1);
   if (!on || !is_bf16 || N < 8 || N % 8) return 0;
   const int nvec = (N / 8 + WAVE - 1) / WAVE;
   return nvec <= LN_RW_MAXVEC ? nvec : 0;
@@ -762,10 +669,113 @@ static int ln_rw_waves(int M, int cap) {
 
 // Waves of the row-per-wave forward grid. 4096 = 16 per CU, all resident.
 static int ln_rw_fwd_waves(int M) {
-  int cap = 4096;
-  if (const char* v = getenv("TDSA_LN_RW_WAVES")) cap = atoi(v);
-  return ln_rw_waves(M, cap);
+  return ln_rw_waves(M, (int)env_int("TDSA_LN_RW_WAVES", 4096));
 }
+
+// Stripe count G for `nvec` vectors per lane (0: not row-per-wave). On the
+// row-per-wave path G is the number of waves in the grid (every wave writes
+// its stripe row).
+static int ln_stripe_count(int M, int nvec) {
+  // within-box sweep: 2048 stripes beat 4096 (dwdb reduce pays per stripe)
+  const int cap = (int)env_int("TDSA_LN_STRIPES", 2048);
+  if (nvec) return ln_rw_waves(M, cap);
+  const int g = M < cap ? M : cap;
+  return g < 1 ? 1 : g;
+}
+
+// Workgroup-per-row block size, matched to the row width: at 256 threads and
+// N=1024 bf16 only 128 lanes have work (tid*W < N) — half the block idled
+// (profiled 2x).
+static int ln_block(int N, int W) {
+  int need = (N + W - 1) / W;
+  int blk = ((need + 63) / 64) * 64;
+  if (blk > 256) blk = 256;
+  if (blk < 64) blk = 64;
+  return blk;
+}
+
+// Workgroup-per-row grid, one row per block up to the cap: chaining rows
+// serializes the per-row reduction barriers; resident blocks overlap freely
+// instead.
+static int ln_wg_grid(int M) {
+  const int cap = (int)env_int("TDSA_LN_GRID", 32768);
+  return M < cap ? M : cap;
+}
+
+// ---- launchers ---------------------------------------------------------------
+// A runtime flag or vector count becomes a template argument by calling `f`
+// with the matching std::integral_constant.
+template <typename F>
+static void ln_with_flag(bool flag, F f) {
+  if (flag) f(std::true_type{}); else f(std::false_type{});
+}
+template <typename F>
+static void ln_rw_with_nvec(int nvec, F f) {
+  static_assert(LN_RW_MAXVEC == 4, "one case per routed vector count");
+  switch (nvec) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+
+// Workgroup-per-row forward; rows past the register cache take the re-reading
+// form at full block size.
+template <typename T>
+static hipError_t ln_fwd_wg(const T* x, const T* res, T* h, const T* w,
+                            const T* b, T* y, float* mean, float* rstd, int M,
+                            int N, float eps, hipStream_t stream) {
+  constexpr int W = VecTraits<T>::W;
+  if (N % W) return hipErrorInvalidValue;  // 16B row-base alignment
+  const int block = ln_block(N, W);
+  const int grid = ln_wg_grid(M);
+  ln_with_flag(res != nullptr, [&](auto has_res) {
+    constexpr bool HAS_RES = decltype(has_res)::value;
+    if (N > LN_WG_MAXITER * block * W)
+      hipLaunchKernelGGL((ln_fwd_kernel<T, HAS_RES, 0>), dim3(grid), dim3(1024),
+                         0, stream, x, res, h, w, b, y, mean, rstd, M, N, eps);
+    else
+      hipLaunchKernelGGL((ln_fwd_kernel<T, HAS_RES, LN_WG_MAXITER>), dim3(grid),
+                         dim3(block), 0, stream, x, res, h, w, b, y, mean, rstd,
+                         M, N, eps);
+  });
+  return hipGetLastError();
+}
+
+// Workgroup-per-row backward: dx at one row per block, then the streaming
+// stripe accumulation at the stripe grid; past the register cache the wide
+// kernel does both at the stripe grid.
+template <typename T>
+static hipError_t ln_bwd_dx_wg(const T* dy, const T* dh, const T* x, const T* w,
+                               const float* mean, const float* rstd, T* dx,
+                               float* pdw, float* pdb, int M, int N,
+                               hipStream_t stream) {
+  constexpr int W = VecTraits<T>::W;
+  if (N % W) return hipErrorInvalidValue;  // 16B row-base alignment
+  const int block = ln_block(N, W);
+  const int stripes = ln_stripe_count(M, 0);
+  const bool wide = N > LN_WG_MAXITER * block * W;
+  const int dx_grid = wide ? stripes : ln_wg_grid(M);
+  ln_with_flag(dh != nullptr, [&](auto has_dh) {
+    constexpr bool HAS_DH = decltype(has_dh)::value;
+    if (wide)
+      hipLaunchKernelGGL((ln_bwd_dx_wide_kernel<T, HAS_DH>), dim3(dx_grid),
+                         dim3(1024), 0, stream, dy, dh, x, w, mean, rstd, dx,
+                         pdw, pdb, M, N);
+    else
+      hipLaunchKernelGGL((ln_bwd_dx_kernel<T, LN_WG_MAXITER, HAS_DH>),
+                         dim3(dx_grid), dim3(block), 0, stream, dy, dh, x, w,
+                         mean, rstd, dx, M, N);
+  });
+  if (!wide)
+    hipLaunchKernelGGL((ln_dwdb_accum_kernel<T, LN_WG_MAXITER>), dim3(stripes),
+                       dim3(block), 0, stream, dy, x, mean, rstd, pdw, pdb, M,
+                       N);
+  return hipGetLastError();
+}
+
+extern "C" {
 
 // Geometry of the row-per-wave path for the tests and tools: forward waves
 // and batch depths for this shape (0 when it is not routed) and the last
@@ -779,16 +789,6 @@ void tdsa_ln_rowwave_info(int M, int N, int is_bf16, int* fwd_waves,
   *bound = LN_RW_MAXVEC * WAVE * 8;
 }
 
-// Block size matched to the row width: at 256 threads and N=1024 bf16 only
-// 128 lanes have work (tid*W < N) — half the block idled (profiled 2x).
-static int ln_block(int N, int W) {
-  int need = (N + W - 1) / W;
-  int blk = ((need + 63) / 64) * 64;
-  if (blk > 256) blk = 256;
-  if (blk < 64) blk = 64;
-  return blk;
-}
-
 // res/h: optional fused residual (pass nullptr for the plain form).
 hipError_t tdsa_ln_fwd(const void* x, const void* res, void* h, const void* w,
                        const void* b, void* y, float* mean, float* rstd,
@@ -796,177 +796,62 @@ hipError_t tdsa_ln_fwd(const void* x, const void* res, void* h, const void* w,
                        hipStream_t stream) {
   if (const int nvec = ln_rw_nvec(N, is_bf16)) {
     const int grid = ln_rw_fwd_waves(M) / LN_RW_WAVES;
-#define LN_RW_FWD(HASR, NV)                                                   \
-  hipLaunchKernelGGL(                                                         \
-      (ln_fwd_rowwave_kernel<bf16, HASR, NV, LN_RW_FWD_DEPTH(NV)>),           \
-      dim3(grid), dim3(LN_RW_BLOCK), 0, stream, (const bf16*)x,               \
-      (const bf16*)res, (bf16*)h, (const bf16*)w, (const bf16*)b, (bf16*)y,   \
-      mean, rstd, M, N, eps)
-#define LN_RW_FWD_NV(NV)                                                      \
-  do {                                                                        \
-    if (res) LN_RW_FWD(true, NV); else LN_RW_FWD(false, NV);                  \
-  } while (0)
-    switch (nvec) {
-      case 1: LN_RW_FWD_NV(1); break;
-      case 2: LN_RW_FWD_NV(2); break;
-      case 3: LN_RW_FWD_NV(3); break;
-      default: LN_RW_FWD_NV(4); break;
-    }
-#undef LN_RW_FWD_NV
-#undef LN_RW_FWD
+    ln_rw_with_nvec(nvec, [&](auto nv) {
+      ln_with_flag(res != nullptr, [&](auto has_res) {
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL(
+            (ln_fwd_rowwave_kernel<bf16, decltype(has_res)::value, NV,
+                                   LN_RW_FWD_DEPTH(NV)>),
+            dim3(grid), dim3(LN_RW_BLOCK), 0, stream, (const bf16*)x,
+            (const bf16*)res, (bf16*)h, (const bf16*)w, (const bf16*)b,
+            (bf16*)y, mean, rstd, M, N, eps);
+      });
+    });
     return hipGetLastError();
   }
-  const int block = ln_block(N, is_bf16 ? 8 : 4);
-  // one row per block up to the cap: chaining rows serializes the per-row
-  // reduction barriers; resident blocks overlap freely instead
-  int cap = 32768;
-  if (const char* v = getenv("TDSA_LN_GRID")) cap = atoi(v);
-  const int grid = (M < cap) ? M : cap;
-  // one-wave rows, one row per 64-thread workgroup: measured 2-3x SLOWER
-  // than the 2-wave block form (a lone wave with one row of loads in
-  // flight loses memory-level parallelism; the row-per-wave kernels above
-  // keep it by batching rows per wave) — kept behind TDSA_LN_WAVE=1 as a
-  // record for the shapes that stay on this path
-  int wave_ok = 0;
-  if (const char* v = getenv("TDSA_LN_WAVE")) wave_ok = atoi(v);
-#define LN_FWD(T, HASR)                                                       \
-  hipLaunchKernelGGL((ln_fwd_kernel<T, HASR>), dim3(grid), dim3(block), 0,    \
-                     stream, (const T*)x, (const T*)res, (T*)h, (const T*)w,  \
-                     (const T*)b, (T*)y, mean, rstd, M, N, eps)
-#define LN_FWD_OW(T, HASR)                                                    \
-  hipLaunchKernelGGL((ln_fwd_kernel<T, HASR, 4, true>), dim3(grid),           \
-                     dim3(WAVE), 0, stream, (const T*)x, (const T*)res,       \
-                     (T*)h, (const T*)w, (const T*)b, (T*)y, mean, rstd, M,   \
-                     N, eps)
-#define LN_FWD_WIDE(T, HASR)                                                  \
-  hipLaunchKernelGGL((ln_fwd_wide_kernel<T, HASR>), dim3(grid), dim3(1024),   \
-                     0, stream, (const T*)x, (const T*)res, (T*)h,            \
-                     (const T*)w, (const T*)b, (T*)y, mean, rstd, M, N, eps)
-  if (is_bf16) {
-    if (N % 8) return hipErrorInvalidValue;  // 16B row-base alignment
-    if (wave_ok && N <= 4 * WAVE * 8) {
-      if (res) LN_FWD_OW(bf16, true); else LN_FWD_OW(bf16, false);
-    } else if (N > 2 * block * 8) {
-      if (res) LN_FWD_WIDE(bf16, true); else LN_FWD_WIDE(bf16, false);
-    } else {
-      if (res) LN_FWD(bf16, true); else LN_FWD(bf16, false);
-    }
-  } else {
-    if (N % 4) return hipErrorInvalidValue;
-    if (wave_ok && N <= 4 * WAVE * 4) {
-      if (res) LN_FWD_OW(float, true); else LN_FWD_OW(float, false);
-    } else if (N > 2 * block * 4) {
-      if (res) LN_FWD_WIDE(float, true); else LN_FWD_WIDE(float, false);
-    } else {
-      if (res) LN_FWD(float, true); else LN_FWD(float, false);
-    }
-  }
-#undef LN_FWD
-#undef LN_FWD_OW
-#undef LN_FWD_WIDE
-  return hipGetLastError();
+  if (is_bf16)
+    return ln_fwd_wg((const bf16*)x, (const bf16*)res, (bf16*)h, (const bf16*)w,
+                     (const bf16*)b, (bf16*)y, mean, rstd, M, N, eps, stream);
+  return ln_fwd_wg((const float*)x, (const float*)res, (float*)h,
+                   (const float*)w, (const float*)b, (float*)y, mean, rstd, M, N,
+                   eps, stream);
 }
 
-// G (stripe count) is chosen here, the single place that decides it, and
-// reported to the caller so it can size pdw/pdb. On the row-per-wave path G
-// is the number of waves in the grid (every wave writes its stripe row).
+// G (stripe count), reported to the caller so it can size pdw/pdb. This and
+// the launcher below both take it from ln_stripe_count, the single place that
+// decides it.
 int tdsa_ln_bwd_dx_stripes(int M, int N, int is_bf16) {
-  // within-box sweep: 2048 stripes beat 4096 (dwdb reduce pays per stripe)
-  int cap = 2048;
-  if (const char* v = getenv("TDSA_LN_STRIPES")) cap = atoi(v);
-  if (ln_rw_nvec(N, is_bf16)) return ln_rw_waves(M, cap);
-  int g = M < cap ? M : cap;
-  return g < 1 ? 1 : g;
+  return ln_stripe_count(M, ln_rw_nvec(N, is_bf16));
 }
 
 // dh: optional residual-stream gradient added into dx (nullptr for plain).
-// Routed shapes run ln_bwd_rowwave_kernel (one pass, no accum kernel). For
-// the rest the default is the SPLIT scheme (dx at full grid + streaming stripe accum;
-// see ln_bwd_dx_kernel comment); TDSA_LN_SPLIT=0 restores the fused form.
+// Routed shapes run ln_bwd_rowwave_kernel (one pass, no accum kernel).
 hipError_t tdsa_ln_bwd_dx(const void* dy, const void* dh, const void* x,
                           const void* w, const float* mean, const float* rstd,
                           void* dx, float* pdw, float* pdb, int M, int N,
                           int is_bf16, hipStream_t stream) {
   if (const int nvec = ln_rw_nvec(N, is_bf16)) {
-    const int grid = tdsa_ln_bwd_dx_stripes(M, N, is_bf16) / LN_RW_WAVES;
-#define LN_RW_BWD(HASD, NV)                                                   \
-  hipLaunchKernelGGL(                                                         \
-      (ln_bwd_rowwave_kernel<bf16, HASD, NV, LN_RW_BWD_DEPTH(NV)>),           \
-      dim3(grid), dim3(LN_RW_BLOCK), 0, stream, (const bf16*)dy,              \
-      (const bf16*)dh, (const bf16*)x, (const bf16*)w, mean, rstd, (bf16*)dx, \
-      pdw, pdb, M, N)
-#define LN_RW_BWD_NV(NV)                                                      \
-  do {                                                                        \
-    if (dh) LN_RW_BWD(true, NV); else LN_RW_BWD(false, NV);                   \
-  } while (0)
-    switch (nvec) {
-      case 1: LN_RW_BWD_NV(1); break;
-      case 2: LN_RW_BWD_NV(2); break;
-      case 3: LN_RW_BWD_NV(3); break;
-      default: LN_RW_BWD_NV(4); break;
-    }
-#undef LN_RW_BWD_NV
-#undef LN_RW_BWD
+    const int grid = ln_stripe_count(M, nvec) / LN_RW_WAVES;
+    ln_rw_with_nvec(nvec, [&](auto nv) {
+      ln_with_flag(dh != nullptr, [&](auto has_dh) {
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL(
+            (ln_bwd_rowwave_kernel<bf16, decltype(has_dh)::value, NV,
+                                   LN_RW_BWD_DEPTH(NV)>),
+            dim3(grid), dim3(LN_RW_BLOCK), 0, stream, (const bf16*)dy,
+            (const bf16*)dh, (const bf16*)x, (const bf16*)w, mean, rstd,
+            (bf16*)dx, pdw, pdb, M, N);
+      });
+    });
     return hipGetLastError();
   }
-  const int block = ln_block(N, is_bf16 ? 8 : 4);
-  const int grid = tdsa_ln_bwd_dx_stripes(M, N, is_bf16);
-  int split = 1;
-  if (const char* v = getenv("TDSA_LN_SPLIT")) split = atoi(v);
-  int dx_cap = 32768;
-  if (const char* v = getenv("TDSA_LN_GRID")) dx_cap = atoi(v);
-  const int dx_grid = split ? ((M < dx_cap) ? M : dx_cap) : grid;
-  int wave_ok = 0;  // measured worse (see tdsa_ln_fwd comment)
-  if (const char* v = getenv("TDSA_LN_WAVE")) wave_ok = atoi(v);
-  const int ow = wave_ok && N <= 4 * WAVE * (is_bf16 ? 8 : 4);
-#define LN_BWD(T, HASD)                                                        \
-  do {                                                                         \
-    if (split && ow) {                                                         \
-      hipLaunchKernelGGL((ln_bwd_dx_kernel<T, 4, HASD, false, true>),          \
-                         dim3(dx_grid), dim3(WAVE), 0, stream, (const T*)dy,   \
-                         (const T*)dh, (const T*)x, (const T*)w, mean, rstd,   \
-                         (T*)dx, pdw, pdb, M, N);                              \
-      hipLaunchKernelGGL((ln_dwdb_accum_kernel<T, 2>), dim3(grid),             \
-                         dim3(block), 0, stream, (const T*)dy, (const T*)x,    \
-                         mean, rstd, pdw, pdb, M, N);                          \
-    } else if (split) {                                                        \
-      hipLaunchKernelGGL((ln_bwd_dx_kernel<T, 2, HASD, false>), dim3(dx_grid), \
-                         dim3(block), 0, stream, (const T*)dy, (const T*)dh,   \
-                         (const T*)x, (const T*)w, mean, rstd, (T*)dx, pdw,    \
-                         pdb, M, N);                                           \
-      hipLaunchKernelGGL((ln_dwdb_accum_kernel<T, 2>), dim3(grid),             \
-                         dim3(block), 0, stream, (const T*)dy, (const T*)x,    \
-                         mean, rstd, pdw, pdb, M, N);                          \
-    } else {                                                                   \
-      hipLaunchKernelGGL((ln_bwd_dx_kernel<T, 2, HASD, true>), dim3(grid),     \
-                         dim3(block), 0, stream, (const T*)dy, (const T*)dh,   \
-                         (const T*)x, (const T*)w, mean, rstd, (T*)dx, pdw,    \
-                         pdb, M, N);                                           \
-    }                                                                          \
-  } while (0)
-#define LN_BWD_WIDE(T, HASD)                                                  \
-  hipLaunchKernelGGL((ln_bwd_dx_wide_kernel<T, HASD>), dim3(grid),            \
-                     dim3(1024), 0, stream, (const T*)dy, (const T*)dh,       \
-                     (const T*)x, (const T*)w, mean, rstd, (T*)dx, pdw, pdb,  \
-                     M, N)
-  if (is_bf16) {
-    if (N % 8) return hipErrorInvalidValue;  // 16B row-base alignment
-    if (N > 2 * block * 8) {
-      if (dh) LN_BWD_WIDE(bf16, true); else LN_BWD_WIDE(bf16, false);
-    } else {
-      if (dh) LN_BWD(bf16, true); else LN_BWD(bf16, false);
-    }
-  } else {
-    if (N % 4) return hipErrorInvalidValue;
-    if (N > 2 * block * 4) {
-      if (dh) LN_BWD_WIDE(float, true); else LN_BWD_WIDE(float, false);
-    } else {
-      if (dh) LN_BWD(float, true); else LN_BWD(float, false);
-    }
-  }
-#undef LN_BWD
-#undef LN_BWD_WIDE
-  return hipGetLastError();
+  if (is_bf16)
+    return ln_bwd_dx_wg((const bf16*)dy, (const bf16*)dh, (const bf16*)x,
+                        (const bf16*)w, mean, rstd, (bf16*)dx, pdw, pdb, M, N,
+                        stream);
+  return ln_bwd_dx_wg((const float*)dy, (const float*)dh, (const float*)x,
+                      (const float*)w, mean, rstd, (float*)dx, pdw, pdb, M, N,
+                      stream);
 }
 
 // out_bf16: write dw/db as bf16 (rounded once from the fp32 sums) instead

@@ -377,7 +377,7 @@ hipError_t tdsa_adamw_step(void* param, const void* grad, float* m, float* v,
                            float wd, long long step, long long n,
                            int param_bf16, int grad_bf16, hipStream_t stream) {
   const int block = 256;
-  const int grid = ln_grid(n, block);
+  const int grid = capped_grid(n, block);
   const float inv_bc1 = 1.0f / (1.0f - powf(b1, (float)step));
   const float inv_bc2 = 1.0f / (1.0f - powf(b2, (float)step));
 #define LAUNCH_ADAMW(PT, GT)                                                  \
@@ -399,7 +399,7 @@ hipError_t tdsa_sgd_step(void* param, const void* grad, float* buf, float* maste
                          int first_step, long long n, int param_bf16,
                          int grad_bf16, hipStream_t stream) {
   const int block = 256;
-  const int grid = ln_grid(n, block);
+  const int grid = capped_grid(n, block);
 #define LAUNCH_SGD(PT, GT)                                                    \
   hipLaunchKernelGGL((sgd_kernel<PT, GT>), dim3(grid), dim3(block), 0, stream, \
                      (PT*)param, (const GT*)grad, buf, master, has_buf,        \

@@ -359,6 +359,69 @@ def test_layernorm_wide_bwd_gpu(N, dtype):
     _close(dx2, xf.grad + dh.float(), tol * 4, f"ln wide dx+dh N={N}")
 
 
+@pytest.mark.parametrize("N,dtype", [(4096, torch.bfloat16),
+                                     (4104, torch.bfloat16),
+                                     (2048, torch.float32),
+                                     (2052, torch.float32)])
+def test_layernorm_cache_boundary_gpu(N, dtype, monkeypatch):
+    """The last register-cached width (256 threads x 2 vectors x 8 bf16 / 4
+    fp32) and the first wide one, against fp64 torch on the same inputs.
+    M = 37 on grids of 8 workgroups and 8 stripes: every workgroup loops
+    over rows and the last round is ragged. The stripe buffers hold NaN
+    before each backward, so a stripe row that is not written shows in
+    dw/db."""
+    monkeypatch.setenv("TDSA_LN_GRID", "8")
+    monkeypatch.setenv("TDSA_LN_STRIPES", "8")
+    M, G = 37, 8
+    tol = 2e-2 if dtype == torch.bfloat16 else 1e-4
+    g = torch.Generator(device="cuda").manual_seed(N)
+    r = lambda *s: torch.randn(*s, device="cuda", generator=g).to(dtype)
+    x, res, dy, dh = r(M, N), r(M, N), r(M, N), r(M, N)
+    w, b = r(N), r(N)
+
+    def close(out, ref, t, name):
+        out = out.double()
+        err = (out - ref).abs().max().item()
+        scale = max(ref.abs().max().item(), 1.0)
+        print(f"{name} N={N}: max err {err:.3e} scale {scale:.3e} tol {t}")
+        assert torch.isfinite(out).all(), f"{name}: non-finite output"
+        assert err <= t * scale, f"{name}: max err {err} vs scale {scale} tol {t}"
+
+    for with_res in (False, True):
+        if with_res:
+            h, y, mean, rstd = ops.layernorm_fwd_res(x, res, w, b)
+            close(h, x.double() + res.double(), tol, "h")
+        else:
+            y, mean, rstd = ops.layernorm_fwd(x, w, b)
+            h = x
+        # reference on the h the kernel wrote (and the backward reads)
+        hd = h.double().requires_grad_(True)
+        wd = w.double().requires_grad_(True)
+        bd = b.double().requires_grad_(True)
+        ref = torch.nn.functional.layer_norm(hd, (N,), wd, bd)
+        ref.backward(dy.double())
+        name = f"res={with_res}"
+        close(y, ref.detach(), tol, f"y {name}")
+        close(mean, hd.detach().mean(-1), tol, f"mean {name}")
+        close(rstd, (hd.detach().var(-1, unbiased=False) + 1e-5).rsqrt(), tol,
+              f"rstd {name}")
+        for with_dh in (False, True):
+            junk = [torch.full((G, N), float("nan"), device="cuda")
+                    for _ in range(2)]
+            torch.cuda.synchronize()
+            del junk
+            dx, ws = ops.layernorm_dx(dy, h, w, mean, rstd,
+                                      dh=dh if with_dh else None)
+            assert ws[0].shape == (G, N) and ws[1].shape == (G, N)
+            dw, db = ops.layernorm_dwdb(ws, dtype=dtype)
+            assert dw.dtype == dtype and db.dtype == dtype
+            name = f"res={with_res} dh={with_dh}"
+            dx_ref = hd.grad + dh.double() if with_dh else hd.grad
+            close(dx, dx_ref, tol * 4, f"dx {name}")
+            close(dw, wd.grad, tol * 4, f"dw {name}")
+            close(db, bd.grad, tol * 4, f"db {name}")
+
+
 @pytest.mark.parametrize("M,N,K", [
     (64, 128, 128),        # single tile, single chunk
     (4096, 1024, 1024),    # multi-split (one slab per split)

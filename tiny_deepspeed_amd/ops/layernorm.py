@@ -2,13 +2,15 @@
 
 Capability parity with the reference's Triton kernels
 (``/root/reference/tiny_deepspeed/core/module/ops/layernorm.py:46-298``),
-re-designed as CDNA4 HIP kernels (csrc/layernorm.hip):
+re-designed as CDNA4 HIP kernels (csrc/kernels/layernorm.hip):
 
   layernorm_fwd   : per-row mean/rstd in fp32, y = (x-mu)*rstd*w + b
-  layernorm_dx    : dx = (w*dy - (xhat*c1 + c2)) * rstd, plus per-workgroup
-                    partial dw/db accumulated into fp32 stripe buffers
-                    (replacing the reference's spin-lock atomic_cas scheme,
-                    SURVEY.md 2.10A, with a conflict-free two-pass reduce)
+  layernorm_dx    : dx = (w*dy - (xhat*c1 + c2)) * rstd, plus partial dw/db
+                    in fp32 stripe buffers, one stripe row per wave
+                    (row-per-wave kernels) or per workgroup (the others); the
+                    launcher picks the stripe count (replacing the
+                    reference's spin-lock atomic_cas scheme, SURVEY.md 2.10A,
+                    with a conflict-free two-pass reduce)
   layernorm_dwdb  : column-reduce of the stripe buffers -> dw[N], db[N]
 
 Dispatch follows the reference's candidate-list architecture
@@ -21,11 +23,6 @@ import torch
 
 from . import _ext
 from .autotuner import default_tuner
-
-# Number of fp32 partial-stripe rows for the dw/db reduction. Each dx
-# workgroup accumulates its rows into stripe (block_id % N_STRIPES); the
-# dwdb kernel column-reduces the stripes. 1024 blocks cover 256 CUs well.
-N_STRIPES = 256
 
 
 # --- forward candidates ----------------------------------------------------
@@ -83,7 +80,7 @@ def layernorm_fwd_res(x, res, weight, bias, eps=1e-5, tuner=None):
 # --- backward-dx candidates ------------------------------------------------
 def ln_dx_hip(dy, x, weight, mean, rstd, dh):
     dx, pdw, pdb = _ext.get_ext().layernorm_bwd_dx(
-        dy.contiguous(), x.contiguous(), weight, mean, rstd, N_STRIPES, dh
+        dy.contiguous(), x.contiguous(), weight, mean, rstd, dh
     )
     return dx, (pdw, pdb)
 
