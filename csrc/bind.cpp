@@ -7,6 +7,8 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "kernels/optim_desc.h"
+
 #include <array>
 #include <cstring>
 #include <vector>
@@ -37,19 +39,10 @@ hipError_t tdsa_ce_fwd(const void*, const long long*, float*, float*, int*,
                        long long, int, long long, int, hipStream_t);
 hipError_t tdsa_ce_bwd(const void*, const long long*, const float*, void*,
                        long long, int, float, long long, int, hipStream_t);
-hipError_t tdsa_adamw_step(void*, const void*, float*, float*, float*, float*,
-                           int, int, float, float, float, float, float,
-                           long long, long long, int, int, hipStream_t);
-hipError_t tdsa_adamw_multi(const void*, long long, int, int, float, float,
-                            float, float, float, long long, hipStream_t);
-int tdsa_adamw_desc_size();
-int tdsa_adamw_chunkref_size();
-int tdsa_sgd_desc_size();
-hipError_t tdsa_sgd_multi(const void*, long long, int, int, float, float,
-                          float, float, int, int, int, hipStream_t);
-hipError_t tdsa_sgd_step(void*, const void*, float*, float*, int, int, float,
-                         float, float, float, int, int, int, long long, int,
-                         int, hipStream_t);
+hipError_t tdsa_adamw_multi(const void*, int, int, int, float, float, float,
+                            float, float, long long, hipStream_t);
+hipError_t tdsa_sgd_multi(const void*, int, int, float, float, float, float,
+                          int, int, hipStream_t);
 hipError_t tdsa_attn_fwd(const void*, const void*, const void*, void*, float*,
                          long long, long long, int, float, const long long*,
                          const long long*, float, unsigned long long,
@@ -299,134 +292,124 @@ at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor targets,
 }
 
 // ---- fused optimizers -----------------------------------------------------
-void adamw_step(at::Tensor param, at::Tensor grad, at::Tensor m, at::Tensor v,
-                at::Tensor master, at::Tensor vmax, bool has_master,
-                bool amsgrad, double lr, double b1, double b2, double eps,
-                double wd, int64_t step) {
-  CHECK_IN(param); CHECK_IN(grad); CHECK_IN(m); CHECK_IN(v);
-  check_hip(tdsa_adamw_step(param.data_ptr(), grad.data_ptr(),
-                            m.data_ptr<float>(), v.data_ptr<float>(),
-                            has_master ? master.data_ptr<float>() : nullptr,
-                            amsgrad ? vmax.data_ptr<float>() : nullptr,
-                            has_master, amsgrad, (float)lr, (float)b1,
-                            (float)b2, (float)eps, (float)wd, step,
-                            param.numel(), dtype_flag(param), dtype_flag(grad),
-                            cur_stream()),
-            "adamw_step");
+// Data pointer of tensor `name` of entry i, after the checks every tensor of
+// a multi-tensor launch must pass. State tensors (`state`) are fp32.
+void* entry_ptr(const char* what, size_t i, const char* name,
+                const at::Tensor& t, int64_t numel, bool state) {
+  TORCH_CHECK(t.is_cuda(), what, ": ", name, "[", i, "] must be on GPU");
+  TORCH_CHECK(t.is_contiguous(), what, ": ", name, "[", i,
+              "] must be contiguous");
+  const auto st = t.scalar_type();
+  TORCH_CHECK(st == at::kFloat || (!state && st == at::kBFloat16), what, ": ",
+              name, "[", i, "] must be float32",
+              state ? "" : " or bfloat16", ", got ", st);
+  TORCH_CHECK(t.numel() == numel, what, ": ", name, "[", i, "] has ",
+              t.numel(), " elements, param[", i, "] has ", numel);
+  return t.data_ptr();
 }
 
-// One fused launch for a whole parameter list (no amsgrad; the python
-// optimizer falls back to per-tensor calls for that).
+float* state_ptr(const char* what, size_t i, const char* name,
+                 const c10::optional<at::Tensor>& t, int64_t numel) {
+  if (!t.has_value()) return nullptr;
+  return (float*)entry_ptr(what, i, name, *t, numel, true);
+}
+
+// The fields every descriptor starts from: param, grad, numel, dtype flags.
+template <typename Desc>
+void fill_param_grad(Desc& d, const char* what, size_t i, const at::Tensor& p,
+                     const at::Tensor& g) {
+  d.numel = p.numel();
+  d.p = entry_ptr(what, i, "param", p, d.numel, false);
+  d.g = entry_ptr(what, i, "grad", g, d.numel, false);
+  d.param_bf16 = dtype_flag(p);
+  d.grad_bf16 = dtype_flag(g);
+}
+
+// Builds the chunk table for `descs`, ships [descs][chunks] as one small
+// device blob and calls launch(blob, ndescs, nchunks).
+template <typename Desc, typename Launch>
+void launch_optim_multi(const char* what, const std::vector<Desc>& descs,
+                        const at::Device& device, Launch launch) {
+  std::vector<tdsa::ChunkRef> chunks;
+  chunks.reserve(1024);
+  for (size_t i = 0; i < descs.size(); ++i) {
+    const long long nch = (descs[i].numel + tdsa::kOptimChunkElems - 1) /
+                          tdsa::kOptimChunkElems;
+    for (long long c = 0; c < nch; ++c) chunks.push_back({(int)i, (int)c});
+  }
+  const size_t desc_bytes = descs.size() * sizeof(Desc);
+  const size_t chunk_bytes = chunks.size() * sizeof(tdsa::ChunkRef);
+  auto host = at::empty({(long long)(desc_bytes + chunk_bytes)},
+                        at::TensorOptions().dtype(at::kByte));
+  std::memcpy(host.data_ptr(), descs.data(), desc_bytes);
+  std::memcpy((char*)host.data_ptr() + desc_bytes, chunks.data(), chunk_bytes);
+  auto dev = host.to(device);
+  check_hip(launch(dev.data_ptr(), (int)descs.size(), (int)chunks.size()),
+            what);
+}
+
+// One fused launch for a whole parameter list. vmaxs: all present (amsgrad)
+// or all absent.
 void adamw_step_multi(std::vector<at::Tensor> params,
                       std::vector<at::Tensor> grads,
                       std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
                       std::vector<c10::optional<at::Tensor>> masters,
+                      std::vector<c10::optional<at::Tensor>> vmaxs,
                       double lr, double b1, double b2, double eps, double wd,
                       int64_t step) {
+  const char* what = "adamw_step_multi";
   const size_t n = params.size();
   TORCH_CHECK(grads.size() == n && ms.size() == n && vs.size() == n &&
-              masters.size() == n, "length mismatch");
+              masters.size() == n && vmaxs.size() == n,
+              what, ": length mismatch");
   if (n == 0) return;
-  struct Desc {  // must mirror AdamTensorDesc in optim.hip
-    void* p; const void* g; float* m; float* v; float* master;
-    long long numel; int param_bf16; int grad_bf16;
-  };
-  struct CRef { int tensor; int chunk; };
-  TORCH_CHECK((int)sizeof(Desc) == tdsa_adamw_desc_size());
-  TORCH_CHECK((int)sizeof(CRef) == tdsa_adamw_chunkref_size());
-  const int chunk_elems = 1 << 16;
-  std::vector<Desc> descs(n);
-  std::vector<CRef> chunks;
-  chunks.reserve(1024);
+  const bool amsgrad = vmaxs[0].has_value();
+  std::vector<tdsa::AdamTensorDesc> descs(n);
   for (size_t i = 0; i < n; ++i) {
-    auto& p = params[i];
-    auto& g = grads[i];
-    Desc d;
-    d.p = p.data_ptr();
-    d.g = g.data_ptr();
-    d.m = ms[i].data_ptr<float>();
-    d.v = vs[i].data_ptr<float>();
-    d.master = masters[i].has_value() ? masters[i]->data_ptr<float>() : nullptr;
-    d.numel = p.numel();
-    d.param_bf16 = dtype_flag(p);
-    d.grad_bf16 = dtype_flag(g);
-    descs[i] = d;
-    const long long nch = (d.numel + chunk_elems - 1) / chunk_elems;
-    for (long long c = 0; c < nch; ++c)
-      chunks.push_back({(int)i, (int)c});
+    auto& d = descs[i];
+    fill_param_grad(d, what, i, params[i], grads[i]);
+    d.m = state_ptr(what, i, "m", ms[i], d.numel);
+    d.v = state_ptr(what, i, "v", vs[i], d.numel);
+    d.master = state_ptr(what, i, "master", masters[i], d.numel);
+    d.vmax = state_ptr(what, i, "vmax", vmaxs[i], d.numel);
+    TORCH_CHECK((d.vmax != nullptr) == amsgrad, what, ": vmax[", i,
+                "] must be given for every entry or for none");
   }
-  const long long desc_bytes = (long long)(n * sizeof(Desc));
-  const long long total = desc_bytes + (long long)(chunks.size() * sizeof(CRef));
-  auto host = at::empty({total}, at::TensorOptions().dtype(at::kByte));
-  std::memcpy(host.data_ptr(), descs.data(), desc_bytes);
-  std::memcpy((char*)host.data_ptr() + desc_bytes, chunks.data(),
-              chunks.size() * sizeof(CRef));
-  auto dev = host.to(params[0].device());
-  check_hip(tdsa_adamw_multi(dev.data_ptr(), desc_bytes, (int)chunks.size(),
-                             chunk_elems, (float)lr, (float)b1, (float)b2,
-                             (float)eps, (float)wd, step, cur_stream()),
-            "adamw_step_multi");
+  launch_optim_multi(what, descs, params[0].device(),
+                     [&](const void* blob, int ndescs, int nchunks) {
+    return tdsa_adamw_multi(blob, ndescs, nchunks, amsgrad, (float)lr,
+                            (float)b1, (float)b2, (float)eps, (float)wd, step,
+                            cur_stream());
+  });
 }
 
+// first[i]: entry i takes its first step (its buf is set to the gradient).
 void sgd_step_multi(std::vector<at::Tensor> params,
                     std::vector<at::Tensor> grads,
                     std::vector<c10::optional<at::Tensor>> bufs,
                     std::vector<c10::optional<at::Tensor>> masters,
-                    double lr, double momentum, double dampening, double wd,
-                    bool nesterov, bool maximize, bool first_step) {
+                    std::vector<bool> first, double lr, double momentum,
+                    double dampening, double wd, bool nesterov,
+                    bool maximize) {
+  const char* what = "sgd_step_multi";
   const size_t n = params.size();
-  TORCH_CHECK(grads.size() == n && bufs.size() == n && masters.size() == n,
-              "length mismatch");
+  TORCH_CHECK(grads.size() == n && bufs.size() == n && masters.size() == n &&
+              first.size() == n, what, ": length mismatch");
   if (n == 0) return;
-  struct Desc {  // must mirror SgdTensorDesc in optim.hip
-    void* p; const void* g; float* buf; float* master;
-    long long numel; int param_bf16; int grad_bf16;
-  };
-  struct CRef { int tensor; int chunk; };
-  TORCH_CHECK((int)sizeof(Desc) == tdsa_sgd_desc_size());
-  const int chunk_elems = 1 << 16;
-  std::vector<Desc> descs(n);
-  std::vector<CRef> chunks;
+  std::vector<tdsa::SgdTensorDesc> descs(n);
   for (size_t i = 0; i < n; ++i) {
-    Desc d;
-    d.p = params[i].data_ptr();
-    d.g = grads[i].data_ptr();
-    d.buf = bufs[i].has_value() ? bufs[i]->data_ptr<float>() : nullptr;
-    d.master = masters[i].has_value() ? masters[i]->data_ptr<float>() : nullptr;
-    d.numel = params[i].numel();
-    d.param_bf16 = dtype_flag(params[i]);
-    d.grad_bf16 = dtype_flag(grads[i]);
-    descs[i] = d;
-    const long long nch = (d.numel + chunk_elems - 1) / chunk_elems;
-    for (long long c = 0; c < nch; ++c) chunks.push_back({(int)i, (int)c});
+    auto& d = descs[i];
+    fill_param_grad(d, what, i, params[i], grads[i]);
+    d.buf = state_ptr(what, i, "buf", bufs[i], d.numel);
+    d.master = state_ptr(what, i, "master", masters[i], d.numel);
+    d.first = first[i];
   }
-  const long long desc_bytes = (long long)(n * sizeof(Desc));
-  const long long total = desc_bytes + (long long)(chunks.size() * sizeof(CRef));
-  auto host = at::empty({total}, at::TensorOptions().dtype(at::kByte));
-  std::memcpy(host.data_ptr(), descs.data(), desc_bytes);
-  std::memcpy((char*)host.data_ptr() + desc_bytes, chunks.data(),
-              chunks.size() * sizeof(CRef));
-  auto dev = host.to(params[0].device());
-  check_hip(tdsa_sgd_multi(dev.data_ptr(), desc_bytes, (int)chunks.size(),
-                           chunk_elems, (float)lr, (float)momentum,
-                           (float)dampening, (float)wd, nesterov, maximize,
-                           first_step, cur_stream()),
-            "sgd_step_multi");
-}
-
-void sgd_step(at::Tensor param, at::Tensor grad, at::Tensor buf,
-              at::Tensor master, bool has_buf, bool has_master, double lr,
-              double momentum, double dampening, double wd, bool nesterov,
-              bool maximize, bool first_step) {
-  CHECK_IN(param); CHECK_IN(grad);
-  check_hip(tdsa_sgd_step(param.data_ptr(), grad.data_ptr(),
-                          has_buf ? buf.data_ptr<float>() : nullptr,
-                          has_master ? master.data_ptr<float>() : nullptr,
-                          has_buf, has_master, (float)lr, (float)momentum,
+  launch_optim_multi(what, descs, params[0].device(),
+                     [&](const void* blob, int ndescs, int nchunks) {
+    return tdsa_sgd_multi(blob, ndescs, nchunks, (float)lr, (float)momentum,
                           (float)dampening, (float)wd, nesterov, maximize,
-                          first_step, param.numel(), dtype_flag(param),
-                          dtype_flag(grad), cur_stream()),
-            "sgd_step");
+                          cur_stream());
+  });
 }
 
 // ---- TN GEMM (linear dW autotuner candidate) ------------------------------
@@ -591,9 +574,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("n_valid"), py::arg("ignore_index"),
           py::arg("out") = py::none());
   mod.def("gemm_tn", &gemm_tn);
-  mod.def("adamw_step", &adamw_step);
   mod.def("adamw_step_multi", &adamw_step_multi);
-  mod.def("sgd_step", &sgd_step);
   mod.def("sgd_step_multi", &sgd_step_multi);
   mod.def("attention_fwd", &attention_fwd, py::arg("q"), py::arg("k"),
           py::arg("v"), py::arg("scale"), py::arg("out") = py::none(),

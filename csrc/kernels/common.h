@@ -34,7 +34,8 @@ DEV_INLINE short8v load8(const bf16* p) {
 DEV_INLINE void store8(bf16* p, short8v v) {
   *reinterpret_cast<short8v*>(p) = v;
 }
-DEV_INLINE float bf_elem(short8v v, int i) {
+template <typename V>  // short4v or short8v
+DEV_INLINE float bf_elem(V v, int i) {
   union { short s; bf16 b; } u; u.s = v[i]; return bf2f(u.b);
 }
 DEV_INLINE short bf_pack(float x) {

@@ -2,330 +2,191 @@
 //
 // The reference's update math is 7+ separate torch kernel launches per
 // parameter (/root/reference/tiny_deepspeed/core/optim/adamw.py:32-59,
-// sgd.py:28-46). Here one kernel per parameter does the whole m/v/p update
-// in a single HBM pass (fp32 state, fp32 master copy for bf16 params), with
-// the reference's per-parameter step-count bug fixed: `step` is the global
+// sgd.py:28-46). Here one launch updates every parameter in a single HBM
+// pass (fp32 state, fp32 master copy for bf16 params): a per-parameter
+// python loop costs ~200 launches x 15us per step (measured). The
+// reference's per-parameter step-count bug is fixed: `step` is the global
 // 1-based optimizer step.
 #include "common.h"
+#include "optim_desc.h"
 
 namespace tdsa {
-
-template <typename PT, typename GT>
-__global__ void adamw_kernel(PT* __restrict__ param, const GT* __restrict__ grad,
-                             float* __restrict__ m, float* __restrict__ v,
-                             float* __restrict__ master, float* __restrict__ vmax,
-                             int has_master, int amsgrad, float lr, float b1,
-                             float b2, float eps, float wd, float inv_bc1,
-                             float inv_bc2, long long n) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = global_tid(); i < n; i += stride) {
-    float g = (float)grad[i];
-    float p = has_master ? master[i] : (float)param[i];
-    p *= (1.0f - lr * wd);
-    float mi = m[i] = m[i] * b1 + (1.0f - b1) * g;
-    float vi = v[i] = v[i] * b2 + (1.0f - b2) * g * g;
-    float vhat;
-    if (amsgrad) {
-      float mx = fmaxf(vmax[i], vi);
-      vmax[i] = mx;
-      vhat = mx * inv_bc2;
-    } else {
-      vhat = vi * inv_bc2;
-    }
-    p -= lr * inv_bc1 * mi / (sqrtf(vhat) + eps);
-    if (has_master) master[i] = p;
-    param[i] = (PT)p;
-  }
-}
-
-template <typename PT, typename GT>
-__global__ void sgd_kernel(PT* __restrict__ param, const GT* __restrict__ grad,
-                           float* __restrict__ buf, float* __restrict__ master,
-                           int has_buf, int has_master, float lr, float momentum,
-                           float dampening, float wd, int nesterov, int maximize,
-                           int first_step, long long n) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = global_tid(); i < n; i += stride) {
-    float g = (float)grad[i];
-    if (maximize) g = -g;
-    float p = has_master ? master[i] : (float)param[i];
-    if (wd != 0.0f) g += wd * p;
-    if (has_buf) {
-      float b = first_step ? g : buf[i] * momentum + (1.0f - dampening) * g;
-      buf[i] = b;
-      g = nesterov ? (g + momentum * b) : b;
-    }
-    p -= lr * g;
-    if (has_master) master[i] = p;
-    param[i] = (PT)p;
-  }
-}
-
-// ---- multi-tensor AdamW ---------------------------------------------------
-// One launch updates every parameter: a per-parameter python loop costs
-// ~200 launches x 15us per step (measured). Descriptors + chunk table are
-// built host-side and shipped as one small device blob.
-struct AdamTensorDesc {
-  void* p;
-  const void* g;
-  float* m;
-  float* v;
-  float* master;     // nullptr when param is fp32
-  long long numel;
-  int param_bf16;
-  int grad_bf16;
-};
-
-struct ChunkRef {
-  int tensor;
-  int chunk;
-};
-
-template <typename PT, typename GT>
-DEV_INLINE void adamw_elem(PT* p, const GT* g, float* m, float* v,
-                           float* master, long long i, float lr, float b1,
-                           float b2, float eps, float wd, float inv_bc1,
-                           float inv_bc2) {
-  float gv = (float)g[i];
-  float pv = master ? master[i] : (float)p[i];
-  pv *= (1.0f - lr * wd);
-  float mi = m[i] = m[i] * b1 + (1.0f - b1) * gv;
-  float vi = v[i] = v[i] * b2 + (1.0f - b2) * gv * gv;
-  pv -= lr * inv_bc1 * mi / (sqrtf(vi * inv_bc2) + eps);
-  if (master) master[i] = pv;
-  p[i] = (PT)pv;
-}
 
 // 4-wide element vectors for params/grads in either dtype.
 template <typename T> struct Vec4;
 template <> struct Vec4<float> {
   typedef f32x4 V;
-  static DEV_INLINE V load(const float* p) { return *reinterpret_cast<const V*>(p); }
   static DEV_INLINE float get(V v, int k) { return v[k]; }
   static DEV_INLINE void set(V& v, int k, float x) { v[k] = x; }
-  static DEV_INLINE void store(float* p, V v) { *reinterpret_cast<V*>(p) = v; }
 };
 template <> struct Vec4<bf16> {
   typedef short4v V;
-  static DEV_INLINE V load(const bf16* p) { return *reinterpret_cast<const V*>(p); }
-  static DEV_INLINE float get(V v, int k) {
-    union { short s; bf16 b; } u; u.s = v[k]; return bf2f(u.b);
-  }
-  static DEV_INLINE void set(V& v, int k, float x) {
-    union { short s; bf16 b; } u; u.b = f2bf(x); v[k] = u.s;
-  }
-  static DEV_INLINE void store(bf16* p, V v) { *reinterpret_cast<V*>(p) = v; }
+  static DEV_INLINE float get(V v, int k) { return bf_elem(v, k); }
+  static DEV_INLINE void set(V& v, int k, float x) { v[k] = bf_pack(x); }
 };
 
-// 4 elements per lane with EXPLICIT dwordx4/dwordx2 accesses: the fp32
-// state (m, v, master) dominates the 10+ GB/step traffic and the
-// element-wise form compiled to scalar flat_load_dword (checked in the .s
-// — the unroll never re-vectorized). HASM as a template so the master
+// One chunk [start, end) of one tensor under `rule`, with S fp32 state
+// streams `st`. 4 elements per lane with EXPLICIT dwordx4/dwordx2 accesses:
+// the fp32 state (m, v, buf, master) dominates the 10+ GB/step traffic and
+// the element-wise form compiled to scalar flat_load_dword (checked in the
+// .s — the unroll never re-vectorized). HASM as a template so the master
 // loads/stores are unconditional in the fast path.
-template <typename PT, typename GT, bool HASM>
-DEV_INLINE void adamw_span_vec(PT* p, const GT* g, float* m, float* v,
-                               float* master, long long start, long long end,
-                               float lr, float b1, float b2, float eps,
-                               float wd, float inv_bc1, float inv_bc2) {
-  const long long n4 = (end - start) / 4;
-  const float decay = 1.0f - lr * wd;
-  for (long long q = threadIdx.x; q < n4; q += blockDim.x) {
-    const long long i = start + q * 4;
-    typename Vec4<GT>::V gv = Vec4<GT>::load(g + i);
-    f32x4 mv = *reinterpret_cast<const f32x4*>(m + i);
-    f32x4 vv = *reinterpret_cast<const f32x4*>(v + i);
-    f32x4 pv;
-    typename Vec4<PT>::V praw;
-    if (HASM) {
-      pv = *reinterpret_cast<const f32x4*>(master + i);
-    } else {
-      praw = Vec4<PT>::load(p + i);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) pv[k] = Vec4<PT>::get(praw, k);
-    }
-    typename Vec4<PT>::V pout;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float gk = Vec4<GT>::get(gv, k);
-      float pk = pv[k] * decay;
-      const float mi = mv[k] = mv[k] * b1 + (1.0f - b1) * gk;
-      const float vi = vv[k] = vv[k] * b2 + (1.0f - b2) * gk * gk;
-      pk -= lr * inv_bc1 * mi / (sqrtf(vi * inv_bc2) + eps);
-      pv[k] = pk;
-      Vec4<PT>::set(pout, k, pk);
-    }
-    *reinterpret_cast<f32x4*>(m + i) = mv;
-    *reinterpret_cast<f32x4*>(v + i) = vv;
-    if (HASM) *reinterpret_cast<f32x4*>(master + i) = pv;
-    Vec4<PT>::store(p + i, pout);
-  }
-  for (long long i = start + n4 * 4 + threadIdx.x; i < end; i += blockDim.x)
-    adamw_elem(p, g, m, v, HASM ? master : nullptr, i, lr, b1, b2, eps, wd,
-               inv_bc1, inv_bc2);
-}
-
-template <typename PT, typename GT>
-DEV_INLINE void adamw_update_span(PT* p, const GT* g, float* m, float* v,
-                                  float* master, long long start, long long end,
-                                  float lr, float b1, float b2, float eps,
-                                  float wd, float inv_bc1, float inv_bc2) {
-  if (master)
-    adamw_span_vec<PT, GT, true>(p, g, m, v, master, start, end, lr, b1, b2,
-                                 eps, wd, inv_bc1, inv_bc2);
-  else
-    adamw_span_vec<PT, GT, false>(p, g, m, v, master, start, end, lr, b1, b2,
-                                  eps, wd, inv_bc1, inv_bc2);
-}
-
-__global__ void adamw_multi_kernel(const AdamTensorDesc* __restrict__ descs,
-                                   const ChunkRef* __restrict__ chunks,
-                                   int nchunks, int chunk_elems, float lr,
-                                   float b1, float b2, float eps, float wd,
-                                   float inv_bc1, float inv_bc2) {
-  for (int cid = blockIdx.x; cid < nchunks; cid += gridDim.x) {
-    const ChunkRef ch = chunks[cid];
-    const AdamTensorDesc d = descs[ch.tensor];
-    const long long start = (long long)ch.chunk * chunk_elems;
-    const long long end = min(d.numel, start + chunk_elems);
-    if (d.param_bf16 && d.grad_bf16)
-      adamw_update_span((bf16*)d.p, (const bf16*)d.g, d.m, d.v, d.master,
-                        start, end, lr, b1, b2, eps, wd, inv_bc1, inv_bc2);
-    else if (d.param_bf16)
-      adamw_update_span((bf16*)d.p, (const float*)d.g, d.m, d.v, d.master,
-                        start, end, lr, b1, b2, eps, wd, inv_bc1, inv_bc2);
-    else if (d.grad_bf16)
-      adamw_update_span((float*)d.p, (const bf16*)d.g, d.m, d.v, d.master,
-                        start, end, lr, b1, b2, eps, wd, inv_bc1, inv_bc2);
-    else
-      adamw_update_span((float*)d.p, (const float*)d.g, d.m, d.v, d.master,
-                        start, end, lr, b1, b2, eps, wd, inv_bc1, inv_bc2);
-  }
-}
-
-DEV_INLINE float sgd_math(float gv, float& pv, float* buf, long long i,
-                          float lr, float momentum, float dampening, float wd,
-                          int nesterov, int maximize, int first_step) {
-  if (maximize) gv = -gv;
-  if (wd != 0.0f) gv += wd * pv;
-  if (buf) {
-    float b = first_step ? gv : buf[i] * momentum + (1.0f - dampening) * gv;
-    buf[i] = b;
-    gv = nesterov ? (gv + momentum * b) : b;
-  }
-  pv -= lr * gv;
-  return pv;
-}
-
-// 4 elements/lane with explicit dwordx4 state accesses (same rationale as
-// adamw_span_vec; the scalar form compiled to flat_load_dword streams).
-template <typename PT, typename GT, bool HASB, bool HASM>
-DEV_INLINE void sgd_span_vec(PT* p, const GT* g, float* buf, float* master,
-                             long long start, long long end, float lr,
-                             float momentum, float dampening, float wd,
-                             int nesterov, int maximize, int first_step) {
+template <int S, bool HASM, typename Rule, typename PT, typename GT>
+DEV_INLINE void update_span(const Rule& rule, PT* p, const GT* g,
+                            const typename Rule::Desc& d, float* const* st,
+                            long long start, long long end) {
+  typedef typename Vec4<PT>::V PV;
+  typedef typename Vec4<GT>::V GV;
+  float* const master = d.master;
   const long long n4 = (end - start) / 4;
   for (long long q = threadIdx.x; q < n4; q += blockDim.x) {
     const long long i = start + q * 4;
-    typename Vec4<GT>::V gv = Vec4<GT>::load(g + i);
+    const GV gv = *reinterpret_cast<const GV*>(g + i);
+    f32x4 sv[S + 1];  // +1: S may be 0
+#pragma unroll
+    for (int j = 0; j < S; ++j)
+      sv[j] = *reinterpret_cast<const f32x4*>(st[j] + i);
     f32x4 pv;
     if (HASM) {
       pv = *reinterpret_cast<const f32x4*>(master + i);
     } else {
-      typename Vec4<PT>::V praw = Vec4<PT>::load(p + i);
+      const PV praw = *reinterpret_cast<const PV*>(p + i);
 #pragma unroll
       for (int k = 0; k < 4; ++k) pv[k] = Vec4<PT>::get(praw, k);
     }
-    f32x4 bv;
-    if (HASB) bv = *reinterpret_cast<const f32x4*>(buf + i);
-    typename Vec4<PT>::V pout;
+    PV pout;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      float gk = Vec4<GT>::get(gv, k);
-      if (maximize) gk = -gk;
-      float pk = pv[k];
-      if (wd != 0.0f) gk += wd * pk;
-      if (HASB) {
-        float b = first_step ? gk : bv[k] * momentum + (1.0f - dampening) * gk;
-        bv[k] = b;
-        gk = nesterov ? (gk + momentum * b) : b;
-      }
-      pk -= lr * gk;
-      pv[k] = pk;
-      Vec4<PT>::set(pout, k, pk);
+      float s[S + 1];
+#pragma unroll
+      for (int j = 0; j < S; ++j) s[j] = sv[j][k];
+      pv[k] = rule.template elem<S>(d, Vec4<GT>::get(gv, k), pv[k], s);
+#pragma unroll
+      for (int j = 0; j < S; ++j) sv[j][k] = s[j];
+      Vec4<PT>::set(pout, k, pv[k]);
     }
-    if (HASB) *reinterpret_cast<f32x4*>(buf + i) = bv;
+#pragma unroll
+    for (int j = 0; j < S; ++j) *reinterpret_cast<f32x4*>(st[j] + i) = sv[j];
     if (HASM) *reinterpret_cast<f32x4*>(master + i) = pv;
-    Vec4<PT>::store(p + i, pout);
+    *reinterpret_cast<PV*>(p + i) = pout;
   }
   for (long long i = start + n4 * 4 + threadIdx.x; i < end; i += blockDim.x) {
-    float pv = HASM ? master[i] : (float)p[i];
-    pv = sgd_math((float)g[i], pv, HASB ? buf : nullptr, i, lr, momentum,
-                  dampening, wd, nesterov, maximize, first_step);
-    if (HASM) master[i] = pv;
-    p[i] = (PT)pv;
+    float s[S + 1];
+#pragma unroll
+    for (int j = 0; j < S; ++j) s[j] = st[j][i];
+    const float pk = rule.template elem<S>(
+        d, (float)g[i], HASM ? master[i] : (float)p[i], s);
+#pragma unroll
+    for (int j = 0; j < S; ++j) st[j][i] = s[j];
+    if (HASM) master[i] = pk;
+    p[i] = (PT)pk;
   }
 }
 
-template <typename PT, typename GT>
-DEV_INLINE void sgd_update_span(PT* p, const GT* g, float* buf, float* master,
-                                long long start, long long end, float lr,
-                                float momentum, float dampening, float wd,
-                                int nesterov, int maximize, int first_step) {
-  if (buf && master)
-    sgd_span_vec<PT, GT, true, true>(p, g, buf, master, start, end, lr,
-                                     momentum, dampening, wd, nesterov,
-                                     maximize, first_step);
-  else if (buf)
-    sgd_span_vec<PT, GT, true, false>(p, g, buf, master, start, end, lr,
-                                      momentum, dampening, wd, nesterov,
-                                      maximize, first_step);
-  else if (master)
-    sgd_span_vec<PT, GT, false, true>(p, g, buf, master, start, end, lr,
-                                      momentum, dampening, wd, nesterov,
-                                      maximize, first_step);
-  else
-    sgd_span_vec<PT, GT, false, false>(p, g, buf, master, start, end, lr,
-                                       momentum, dampening, wd, nesterov,
-                                       maximize, first_step);
-}
+// ---- update rules ----------------------------------------------------------
+// A rule is the kernel argument of optim_multi_kernel: the hyper-parameters,
+// elem() — the per-element math on registers, which updates the element's S
+// fp32 state values `s` in place and returns the new parameter — and
+// chunk(), which picks the compile-time update_span variant for one tensor.
+//
+// elem() spells out its roundings (contraction off, explicit fmaf) so that
+// the vector body and the scalar tail of every dtype variant round alike,
+// whatever the vectorizer makes of the surrounding code.
+template <bool AMS>
+struct AdamW {
+  typedef AdamTensorDesc Desc;
+  float lr, b1, b2, eps, wd, inv_bc1, inv_bc2;
 
-struct SgdTensorDesc {
-  void* p;
-  const void* g;
-  float* buf;        // nullptr without momentum
-  float* master;     // nullptr when param is fp32
-  long long numel;
-  int param_bf16;
-  int grad_bf16;
+  // s = {m, v} or, with amsgrad, {m, v, vmax}
+  template <int S>
+  DEV_INLINE float elem(const Desc&, float g, float p, float* s) const {
+#pragma clang fp contract(off)
+    const float m = s[0] = fmaf(1.0f - b1, g, s[0] * b1);
+    float v = s[1] = fmaf(s[1], b2, (1.0f - b2) * g * g);
+    if (AMS) v = s[2] = fmaxf(s[2], v);
+    const float step = lr * inv_bc1 * m / (sqrtf(v * inv_bc2) + eps);
+    return fmaf(p, fmaf(-lr, wd, 1.0f), -step);
+  }
+
+  template <typename PT, typename GT>
+  DEV_INLINE void chunk(PT* p, const GT* g, const Desc& d, long long start,
+                        long long end) const {
+    constexpr int S = AMS ? 3 : 2;
+    float* const st[3] = {d.m, d.v, d.vmax};
+    if (d.master)
+      update_span<S, true>(*this, p, g, d, st, start, end);
+    else
+      update_span<S, false>(*this, p, g, d, st, start, end);
+  }
 };
 
-__global__ void sgd_multi_kernel(const SgdTensorDesc* __restrict__ descs,
-                                 const ChunkRef* __restrict__ chunks,
-                                 int nchunks, int chunk_elems, float lr,
-                                 float momentum, float dampening, float wd,
-                                 int nesterov, int maximize, int first_step) {
+struct Sgd {
+  typedef SgdTensorDesc Desc;
+  float lr, momentum, dampening, wd;
+  int nesterov, maximize;
+
+  // s = {buf} with momentum (S = 1), empty without
+  template <int S>
+  DEV_INLINE float elem(const Desc& d, float g, float p, float* s) const {
+#pragma clang fp contract(off)
+    if (maximize) g = -g;
+    if (wd != 0.0f) g = fmaf(wd, p, g);
+    if (S) {
+      const float b = d.first ? g : s[0] * momentum + (1.0f - dampening) * g;
+      s[0] = b;
+      g = nesterov ? fmaf(momentum, b, g) : b;
+    }
+    return fmaf(-lr, g, p);
+  }
+
+  template <typename PT, typename GT>
+  DEV_INLINE void chunk(PT* p, const GT* g, const Desc& d, long long start,
+                        long long end) const {
+    float* const st[1] = {d.buf};
+    if (d.buf && d.master)
+      update_span<1, true>(*this, p, g, d, st, start, end);
+    else if (d.buf)
+      update_span<1, false>(*this, p, g, d, st, start, end);
+    else if (d.master)
+      update_span<0, true>(*this, p, g, d, st, start, end);
+    else
+      update_span<0, false>(*this, p, g, d, st, start, end);
+  }
+};
+
+// The chunk loop and the (param, grad) dtype ladder of both optimizers.
+template <typename Rule>
+__global__ void optim_multi_kernel(
+    const typename Rule::Desc* __restrict__ descs,
+    const ChunkRef* __restrict__ chunks, int nchunks, int chunk_elems,
+    Rule rule) {
   for (int cid = blockIdx.x; cid < nchunks; cid += gridDim.x) {
     const ChunkRef ch = chunks[cid];
-    const SgdTensorDesc d = descs[ch.tensor];
+    const typename Rule::Desc d = descs[ch.tensor];
     const long long start = (long long)ch.chunk * chunk_elems;
     const long long end = min(d.numel, start + chunk_elems);
     if (d.param_bf16 && d.grad_bf16)
-      sgd_update_span((bf16*)d.p, (const bf16*)d.g, d.buf, d.master, start,
-                      end, lr, momentum, dampening, wd, nesterov, maximize,
-                      first_step);
+      rule.chunk((bf16*)d.p, (const bf16*)d.g, d, start, end);
     else if (d.param_bf16)
-      sgd_update_span((bf16*)d.p, (const float*)d.g, d.buf, d.master, start,
-                      end, lr, momentum, dampening, wd, nesterov, maximize,
-                      first_step);
+      rule.chunk((bf16*)d.p, (const float*)d.g, d, start, end);
     else if (d.grad_bf16)
-      sgd_update_span((float*)d.p, (const bf16*)d.g, d.buf, d.master, start,
-                      end, lr, momentum, dampening, wd, nesterov, maximize,
-                      first_step);
+      rule.chunk((float*)d.p, (const bf16*)d.g, d, start, end);
     else
-      sgd_update_span((float*)d.p, (const float*)d.g, d.buf, d.master, start,
-                      end, lr, momentum, dampening, wd, nesterov, maximize,
-                      first_step);
+      rule.chunk((float*)d.p, (const float*)d.g, d, start, end);
   }
+}
+
+// Grid sizing, blob split and launch.
+template <typename Rule>
+hipError_t launch_multi(const Rule& rule, const void* blob, int ndescs,
+                        int nchunks, hipStream_t stream) {
+  const typename Rule::Desc* descs = (const typename Rule::Desc*)blob;
+  const ChunkRef* chunks = (const ChunkRef*)(descs + ndescs);
+  int grid = nchunks < 2048 ? nchunks : 2048;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(optim_multi_kernel<Rule>, dim3(grid), dim3(256), 0,
+                     stream, descs, chunks, nchunks, kOptimChunkElems, rule);
+  return hipGetLastError();
 }
 
 }  // namespace tdsa
@@ -334,83 +195,25 @@ using namespace tdsa;
 
 extern "C" {
 
-int tdsa_sgd_desc_size() { return (int)sizeof(SgdTensorDesc); }
-
-hipError_t tdsa_sgd_multi(const void* blob, long long desc_bytes, int nchunks,
-                          int chunk_elems, float lr, float momentum,
-                          float dampening, float wd, int nesterov, int maximize,
-                          int first_step, hipStream_t stream) {
-  const SgdTensorDesc* descs = (const SgdTensorDesc*)blob;
-  const ChunkRef* chunks = (const ChunkRef*)((const char*)blob + desc_bytes);
-  int grid = nchunks < 2048 ? nchunks : 2048;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(sgd_multi_kernel, dim3(grid), dim3(256), 0, stream, descs,
-                     chunks, nchunks, chunk_elems, lr, momentum, dampening, wd,
-                     nesterov, maximize, first_step);
-  return hipGetLastError();
-}
-
-// blob layout: [ndescs x AdamTensorDesc][nchunks x ChunkRef], device memory.
-hipError_t tdsa_adamw_multi(const void* blob, long long desc_bytes, int nchunks,
-                            int chunk_elems, float lr, float b1, float b2,
+// amsgrad: every descriptor carries a vmax.
+hipError_t tdsa_adamw_multi(const void* blob, int ndescs, int nchunks,
+                            int amsgrad, float lr, float b1, float b2,
                             float eps, float wd, long long step,
                             hipStream_t stream) {
-  const AdamTensorDesc* descs = (const AdamTensorDesc*)blob;
-  const ChunkRef* chunks =
-      (const ChunkRef*)((const char*)blob + desc_bytes);
   const float inv_bc1 = 1.0f / (1.0f - powf(b1, (float)step));
   const float inv_bc2 = 1.0f / (1.0f - powf(b2, (float)step));
-  int grid = nchunks < 2048 ? nchunks : 2048;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(adamw_multi_kernel, dim3(grid), dim3(256), 0, stream,
-                     descs, chunks, nchunks, chunk_elems, lr, b1, b2, eps, wd,
-                     inv_bc1, inv_bc2);
-  return hipGetLastError();
+  if (amsgrad)
+    return launch_multi(AdamW<true>{lr, b1, b2, eps, wd, inv_bc1, inv_bc2},
+                        blob, ndescs, nchunks, stream);
+  return launch_multi(AdamW<false>{lr, b1, b2, eps, wd, inv_bc1, inv_bc2},
+                      blob, ndescs, nchunks, stream);
 }
 
-int tdsa_adamw_desc_size() { return (int)sizeof(AdamTensorDesc); }
-int tdsa_adamw_chunkref_size() { return (int)sizeof(ChunkRef); }
-
-hipError_t tdsa_adamw_step(void* param, const void* grad, float* m, float* v,
-                           float* master, float* vmax, int has_master,
-                           int amsgrad, float lr, float b1, float b2, float eps,
-                           float wd, long long step, long long n,
-                           int param_bf16, int grad_bf16, hipStream_t stream) {
-  const int block = 256;
-  const int grid = capped_grid(n, block);
-  const float inv_bc1 = 1.0f / (1.0f - powf(b1, (float)step));
-  const float inv_bc2 = 1.0f / (1.0f - powf(b2, (float)step));
-#define LAUNCH_ADAMW(PT, GT)                                                  \
-  hipLaunchKernelGGL((adamw_kernel<PT, GT>), dim3(grid), dim3(block), 0,      \
-                     stream, (PT*)param, (const GT*)grad, m, v, master, vmax, \
-                     has_master, amsgrad, lr, b1, b2, eps, wd, inv_bc1,       \
-                     inv_bc2, n)
-  if (param_bf16 && grad_bf16) LAUNCH_ADAMW(bf16, bf16);
-  else if (param_bf16) LAUNCH_ADAMW(bf16, float);
-  else if (grad_bf16) LAUNCH_ADAMW(float, bf16);
-  else LAUNCH_ADAMW(float, float);
-#undef LAUNCH_ADAMW
-  return hipGetLastError();
-}
-
-hipError_t tdsa_sgd_step(void* param, const void* grad, float* buf, float* master,
-                         int has_buf, int has_master, float lr, float momentum,
-                         float dampening, float wd, int nesterov, int maximize,
-                         int first_step, long long n, int param_bf16,
-                         int grad_bf16, hipStream_t stream) {
-  const int block = 256;
-  const int grid = capped_grid(n, block);
-#define LAUNCH_SGD(PT, GT)                                                    \
-  hipLaunchKernelGGL((sgd_kernel<PT, GT>), dim3(grid), dim3(block), 0, stream, \
-                     (PT*)param, (const GT*)grad, buf, master, has_buf,        \
-                     has_master, lr, momentum, dampening, wd, nesterov,        \
-                     maximize, first_step, n)
-  if (param_bf16 && grad_bf16) LAUNCH_SGD(bf16, bf16);
-  else if (param_bf16) LAUNCH_SGD(bf16, float);
-  else if (grad_bf16) LAUNCH_SGD(float, bf16);
-  else LAUNCH_SGD(float, float);
-#undef LAUNCH_SGD
-  return hipGetLastError();
+hipError_t tdsa_sgd_multi(const void* blob, int ndescs, int nchunks, float lr,
+                          float momentum, float dampening, float wd,
+                          int nesterov, int maximize, hipStream_t stream) {
+  return launch_multi(Sgd{lr, momentum, dampening, wd, nesterov, maximize},
+                      blob, ndescs, nchunks, stream);
 }
 
 }  // extern "C"

@@ -727,3 +727,249 @@ def test_attention_fp32_composite_path_gpu():
     _close(out, ref, 1e-4, "fp32 composite attn")
     out.sum().backward()
     assert torch.isfinite(q.grad).all()
+
+
+# ---- multi-tensor optimizer launches (csrc/kernels/optim.hip) ---------------
+# Every stream of a case (p, g, m, v, vmax, buf, master) is carved out of one
+# flat allocation with the same layout: each view starts at a multiple of 8
+# elements (16-byte aligned in both dtypes) and is followed by at least 8
+# guard elements. The fp64 reference is evaluated on the whole flat streams.
+
+_OPT_CHUNK = 65536
+_OPT_GUARD = -7.0   # exact in bf16 and fp32
+
+
+class _Carved:
+    def __init__(self, numels):
+        self.numels = list(numels)
+        self.offsets, off = [], 8
+        for n in self.numels:
+            self.offsets.append(off)
+            off += (n + 7) // 8 * 8 + 8
+        self.total = off
+        self.mask = torch.zeros(self.total, dtype=torch.bool, device="cuda")
+        for o, n in zip(self.offsets, self.numels):
+            self.mask[o:o + n] = True
+
+    def stream(self, dtype, gen, absolute=False):
+        """(flat, views): data elements randn (|randn| if absolute), guards
+        the sentinel."""
+        data = torch.randn(self.total, device="cuda", generator=gen)
+        if absolute:
+            data = data.abs()
+        flat = torch.where(self.mask, data,
+                           torch.full_like(data, _OPT_GUARD)).to(dtype)
+        return flat, [flat[o:o + n] for o, n in zip(self.offsets, self.numels)]
+
+    def per_tensor(self, values):
+        """Flat tensor holding values[i] on every element of view i."""
+        out = torch.zeros(self.total, dtype=torch.bool, device="cuda")
+        for o, n, val in zip(self.offsets, self.numels, values):
+            out[o:o + n] = val
+        return out
+
+    def check_guards(self, flat, name):
+        g = flat[~self.mask]
+        assert torch.equal(g, torch.full_like(g, _OPT_GUARD)), \
+            f"{name}: guard elements overwritten"
+
+    def close(self, flat, ref, name):
+        _close(flat[self.mask], ref[self.mask], 1e-6, name)
+
+
+def _adamw_ref64(p, g, m, v, vmax, lr, b1, b2, eps, wd, step):
+    """fp64 evaluation of ops.optim_ops.adamw_step on flat streams."""
+    p = p * (1.0 - lr * wd)
+    m = m * b1 + (1.0 - b1) * g
+    v = v * b2 + (1.0 - b2) * g * g
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    if vmax is not None:
+        vmax = torch.maximum(vmax, v)
+        denom = (vmax / bc2).sqrt() + eps
+    else:
+        denom = (v / bc2).sqrt() + eps
+    return p - (lr / bc1) * m / denom, m, v, vmax
+
+
+def _sgd_ref64(p, g, buf, first, lr, momentum, dampening, wd, nesterov,
+               maximize):
+    """fp64 evaluation of ops.optim_ops.sgd_step on flat streams; `first` is
+    the per-element first-step flag."""
+    if maximize:
+        g = -g
+    if wd != 0.0:
+        g = g + wd * p
+    if buf is not None:
+        buf = torch.where(first, g, buf * momentum + (1.0 - dampening) * g)
+        g = g + momentum * buf if nesterov else buf
+    return p - lr * g, buf
+
+
+def _run_adamw_case(numels, pdt, gdt, amsgrad):
+    lay = _Carved(numels)
+    gen = torch.Generator(device="cuda").manual_seed(len(numels))
+    pf, ps = lay.stream(pdt, gen)
+    gf, gs = lay.stream(gdt, gen)
+    mf, ms = lay.stream(torch.float32, gen)
+    vf, vs = lay.stream(torch.float32, gen, absolute=True)
+    xf, xs = lay.stream(torch.float32, gen, absolute=True)
+    has_master = pdt == torch.bfloat16
+    wf = pf.float().clone()
+    ws = [wf[o:o + n] for o, n in zip(lay.offsets, lay.numels)]
+    lr, b1, b2, eps, wd, step = 1e-3, 0.9, 0.999, 1e-8, 0.01, 3
+    rp, rm, rv, rx = _adamw_ref64(
+        pf.double(), gf.double(), mf.double(), vf.double(),
+        xf.double() if amsgrad else None, lr, b1, b2, eps, wd, step)
+    x0 = xf.clone()
+    n = len(numels)
+    _ext.get_ext().adamw_step_multi(
+        ps, gs, ms, vs, ws if has_master else [None] * n,
+        xs if amsgrad else [None] * n, lr, b1, b2, eps, wd, step)
+    name = f"adamw {pdt}/{gdt} ams={amsgrad}"
+    for flat, nm in ((pf, "p"), (gf, "g"), (mf, "m"), (vf, "v"), (xf, "vmax"),
+                     (wf, "master")):
+        lay.check_guards(flat, f"{name} {nm}")
+    lay.close(mf, rm, f"{name} m")
+    lay.close(vf, rv, f"{name} v")
+    if amsgrad:
+        lay.close(xf, rx, f"{name} vmax")
+    else:
+        assert torch.equal(xf, x0), f"{name}: vmax touched without amsgrad"
+    if has_master:
+        lay.close(wf, rp, f"{name} master")
+        assert torch.equal(pf[lay.mask], wf.to(torch.bfloat16)[lay.mask]), \
+            f"{name}: p is not the bf16 rounding of master"
+    else:
+        lay.close(pf, rp, f"{name} p")
+
+
+def _run_sgd_case(numels, pdt, gdt, momentum, dampening, wd, nesterov,
+                  maximize):
+    lay = _Carved(numels)
+    gen = torch.Generator(device="cuda").manual_seed(len(numels) + 1)
+    pf, ps = lay.stream(pdt, gen)
+    gf, gs = lay.stream(gdt, gen)
+    bf, bs = lay.stream(torch.float32, gen)
+    has_master = pdt == torch.bfloat16
+    has_buf = momentum != 0.0
+    wf = pf.float().clone()
+    ws = [wf[o:o + n] for o, n in zip(lay.offsets, lay.numels)]
+    n = len(numels)
+    first = [i % 3 == 1 for i in range(n)]   # mixed inside the one launch
+    lr = 0.1
+    rp, rb = _sgd_ref64(pf.double(), gf.double(),
+                        bf.double() if has_buf else None,
+                        lay.per_tensor(first), lr, momentum, dampening, wd,
+                        nesterov, maximize)
+    b0 = bf.clone()
+    _ext.get_ext().sgd_step_multi(
+        ps, gs, bs if has_buf else [None] * n,
+        ws if has_master else [None] * n, first, lr, momentum, dampening, wd,
+        nesterov, maximize)
+    name = (f"sgd {pdt}/{gdt} mom={momentum} wd={wd} nesterov={nesterov} "
+            f"maximize={maximize}")
+    for flat, nm in ((pf, "p"), (gf, "g"), (bf, "buf"), (wf, "master")):
+        lay.check_guards(flat, f"{name} {nm}")
+    if has_buf:
+        lay.close(bf, rb, f"{name} buf")
+    else:
+        assert torch.equal(bf, b0), f"{name}: buf touched without momentum"
+    if has_master:
+        lay.close(wf, rp, f"{name} master")
+        assert torch.equal(pf[lay.mask], wf.to(torch.bfloat16)[lay.mask]), \
+            f"{name}: p is not the bf16 rounding of master"
+    else:
+        lay.close(pf, rp, f"{name} p")
+
+
+# all tail / exactly one vector / vector + tail / a full chunk / one chunk
+# boundary with a ragged tail / three chunks
+_OPT_NUMELS = [1, 3, 4, 7, _OPT_CHUNK, _OPT_CHUNK + 5, 2 * _OPT_CHUNK + 4]
+_OPT_DTYPES = [(torch.bfloat16, torch.bfloat16), (torch.bfloat16, torch.float32),
+               (torch.float32, torch.bfloat16), (torch.float32, torch.float32)]
+
+
+@pytest.mark.parametrize("amsgrad", [False, True])
+@pytest.mark.parametrize("pdt,gdt", _OPT_DTYPES)
+def test_adamw_multi_chunks_and_tails_gpu(pdt, gdt, amsgrad):
+    _run_adamw_case(_OPT_NUMELS, pdt, gdt, amsgrad)
+
+
+@pytest.mark.parametrize("momentum,dampening,wd,nesterov,maximize", [
+    (0.0, 0.0, 0.01, False, False),     # no buf
+    (0.9, 0.1, 0.01, False, False),
+    (0.9, 0.0, 0.0, True, False),
+    (0.9, 0.1, 0.01, False, True),
+])
+@pytest.mark.parametrize("pdt,gdt", _OPT_DTYPES)
+def test_sgd_multi_chunks_and_tails_gpu(pdt, gdt, momentum, dampening, wd,
+                                        nesterov, maximize):
+    _run_sgd_case(_OPT_NUMELS, pdt, gdt, momentum, dampening, wd, nesterov,
+                  maximize)
+
+
+@pytest.mark.parametrize("opt", ["adamw", "sgd"])
+def test_optim_multi_grid_stride_gpu(opt):
+    """2100 one-chunk tensors: more chunks than the 2048-workgroup grid cap,
+    so some workgroups take a second chunk."""
+    numels = [i % 9 + 1 for i in range(2100)]
+    if opt == "adamw":
+        _run_adamw_case(numels, torch.bfloat16, torch.bfloat16, False)
+    else:
+        _run_sgd_case(numels, torch.bfloat16, torch.bfloat16, 0.9, 0.0, 0.01,
+                      False, False)
+
+
+def test_sgd_late_gradient_gpu():
+    """A parameter whose first gradient arrives on step 2 takes its first
+    momentum step while its neighbour takes its second, in one launch;
+    against the same optimizer on CPU copies (the torch branch)."""
+    from tiny_deepspeed_amd import SGD
+
+    torch.manual_seed(0)
+    cpu = [torch.nn.Parameter(torch.randn(s)) for s in [(33,), (5, 7)]]
+    gpu = [torch.nn.Parameter(t.detach().to("cuda")) for t in cpu]
+    kw = dict(lr=0.1, momentum=0.9, weight_decay=0.01)
+    o_cpu = SGD([(f"p{i}", p) for i, p in enumerate(cpu)], **kw)
+    o_gpu = SGD([(f"p{i}", p) for i, p in enumerate(gpu)], **kw)
+    for it in range(3):
+        for i, (a, b) in enumerate(zip(cpu, gpu)):
+            if it == 0 and i == 1:
+                continue
+            a.grad = torch.randn_like(a)
+            b.grad = a.grad.to("cuda")
+        o_cpu.step()
+        o_gpu.step()
+    for name in o_cpu.params:
+        _close(o_gpu.params[name].data.cpu(), o_cpu.params[name].data, 1e-6,
+               f"late grad {name}")
+        _close(o_gpu.velocities[name].cpu(), o_cpu.velocities[name], 1e-6,
+               f"late grad buf {name}")
+
+
+@pytest.mark.parametrize("bad", ["noncontiguous", "numel", "bf16_m"])
+def test_adamw_multi_rejects_bad_entry_gpu(bad):
+    """The binding checks every entry before it launches: a rejected list
+    leaves all of its tensors untouched."""
+    torch.manual_seed(0)
+    ps = [torch.randn(8, 8, device="cuda") for _ in range(2)]
+    gs = [torch.randn(8, 8, device="cuda") for _ in range(2)]
+    ms = [torch.randn(8, 8, device="cuda") for _ in range(2)]
+    vs = [torch.randn(8, 8, device="cuda").abs() for _ in range(2)]
+    if bad == "noncontiguous":
+        ps[1] = ps[1].t()
+        match = r"param\[1\] must be contiguous"
+    elif bad == "numel":
+        gs[1] = torch.randn(63, device="cuda")
+        match = r"grad\[1\] has 63 elements"
+    else:
+        ms[1] = ms[1].to(torch.bfloat16)
+        match = r": m\[1\] must be float32"
+    before = [t.clone() for t in ps + ms + vs]
+    with pytest.raises(RuntimeError, match=match):
+        _ext.get_ext().adamw_step_multi(ps, gs, ms, vs, [None, None],
+                                        [None, None], 1e-3, 0.9, 0.999, 1e-8,
+                                        0.01, 1)
+    torch.cuda.synchronize()
+    for t, b in zip(ps + ms + vs, before):
+        assert torch.equal(t, b)

@@ -2,8 +2,9 @@
 
 The reference's AdamW/SGD update math is a chain of 7+ torch kernel launches
 per parameter (``/root/reference/tiny_deepspeed/core/optim/adamw.py:32-59``,
-``sgd.py:28-46``). Here each update is ONE CDNA4 kernel (csrc/optim.hip):
-m, v, bias-correction and the parameter write happen in a single HBM pass.
+``sgd.py:28-46``). Here each update is ONE CDNA4 kernel
+(csrc/kernels/optim.hip, the multi-tensor launch with a list of one): m, v,
+bias-correction and the parameter write happen in a single HBM pass.
 Optimizer state (m, v, momentum) is fp32; when the parameter is bf16 a
 separate fp32 master copy is updated and the bf16 param is written from it.
 
@@ -24,13 +25,10 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, master, step, lr, beta1, beta2,
     (None for fp32 params). `step` is the 1-based global step count.
     `max_exp_avg_sq` enables amsgrad."""
     if _ext.use_native(param):
-        _ext.get_ext().adamw_step(
-            param, grad, exp_avg, exp_avg_sq,
-            master if master is not None else param,
-            max_exp_avg_sq if max_exp_avg_sq is not None else exp_avg,
-            master is not None, max_exp_avg_sq is not None,
-            float(lr), float(beta1), float(beta2), float(eps),
-            float(weight_decay), int(step),
+        _ext.get_ext().adamw_step_multi(
+            [param], [grad], [exp_avg], [exp_avg_sq], [master],
+            [max_exp_avg_sq], float(lr), float(beta1), float(beta2),
+            float(eps), float(weight_decay), int(step),
         )
         return
     p32 = master if master is not None else param
@@ -54,14 +52,10 @@ def sgd_step(param, grad, momentum_buf, master, lr, momentum, dampening,
              weight_decay, nesterov, maximize, first_step):
     """In-place SGD update matching torch.optim.SGD semantics."""
     if _ext.use_native(param):
-        _ext.get_ext().sgd_step(
-            param, grad,
-            momentum_buf if momentum_buf is not None else param,
-            master if master is not None else param,
-            momentum_buf is not None, master is not None,
+        _ext.get_ext().sgd_step_multi(
+            [param], [grad], [momentum_buf], [master], [bool(first_step)],
             float(lr), float(momentum), float(dampening),
             float(weight_decay), bool(nesterov), bool(maximize),
-            bool(first_step),
         )
         return
     p32 = master if master is not None else param

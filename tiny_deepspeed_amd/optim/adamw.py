@@ -48,19 +48,19 @@ class AdamW(Optimizer):
 
     @torch.no_grad()
     def _apply_updates(self, items):
-        if (not items or self.amsgrad or not items[0][1].is_cuda
-                or not ops.ext_available()):
+        if not items or not items[0][1].is_cuda or not ops.ext_available():
             return super()._apply_updates(items)
-        params, grads, ms, vs, masters = [], [], [], [], []
+        params, grads, ms, vs, masters, vmaxs = [], [], [], [], [], []
         for name, p in items:
             params.append(p.data)
             grads.append(p.grad)
             ms.append(self.exp_avg[name])
             vs.append(self.exp_avg_sq[name])
             masters.append(self.master.get(name))
+            vmaxs.append(self.max_exp_avg_sq.get(name))
         ops.get_ext().adamw_step_multi(
-            params, grads, ms, vs, masters, self.lr, self.beta1, self.beta2,
-            self.eps, self.weight_decay, self.t,
+            params, grads, ms, vs, masters, vmaxs, self.lr, self.beta1,
+            self.beta2, self.eps, self.weight_decay, self.t,
         )
 
     @torch.no_grad()
