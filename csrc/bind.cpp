@@ -435,41 +435,46 @@ at::Tensor gemm_tn(at::Tensor dy2, at::Tensor x2) {
 }
 
 // ---- attention ------------------------------------------------------------
-static void check_attn_tensor(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.dim() == 4 && t.size(3) == 64, name,
-              ": attention kernel requires (B,H,T,64)");
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
-  TORCH_CHECK(t.stride(3) == 1, name, " last dim must be contiguous");
+// One pass over an attention call's bf16 tensors, q first. The kernels use
+// q's extents and, per group, one tensor's strides (`lead`: q for q/k/v, o for
+// o/dout, dq for dq/dk/dv), so any other shape or stride stops here.
+struct AttnTensor { const char* name; const at::Tensor &t, &lead; };
+static void check_attn_call(std::initializer_list<AttnTensor> tensors,
+                            double dropout_p) {
+  const at::Tensor& q = tensors.begin()->t;
+  for (const auto& [name, t, lead] : tensors) {
+    TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+    TORCH_CHECK(t.dim() == 4 && t.size(3) == 64, name,
+                ": attention kernel requires (B,H,T,64)");
+    TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
+    TORCH_CHECK(t.stride(3) == 1, name, " last dim must be contiguous");
+    TORCH_CHECK(t.sizes() == q.sizes(), name, " must have q's sizes ",
+                q.sizes(), ", got ", t.sizes());
+    TORCH_CHECK(t.strides() == lead.strides(), name,
+                ": q/k/v, o/dout and dq/dk/dv must each share strides");
+  }
+  TORCH_CHECK(q.size(2) % 64 == 0, "attention kernel requires T % 64 == 0");
+  TORCH_CHECK(dropout_p >= 0.0 && dropout_p < 1.0, "bad dropout_p");
 }
 
 static std::array<long long, 3> strides3(const at::Tensor& t) {
-  return {(long long)t.stride(0), (long long)t.stride(1),
-          (long long)t.stride(2)};
+  return {t.stride(0), t.stride(1), t.stride(2)};
 }
 
 std::vector<at::Tensor> attention_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                       double scale,
                                       c10::optional<at::Tensor> out,
                                       double dropout_p, int64_t seed) {
-  check_attn_tensor(q, "q");
-  check_attn_tensor(k, "k");
-  check_attn_tensor(v, "v");
-  TORCH_CHECK(q.strides() == k.strides() && q.strides() == v.strides(),
-              "q/k/v must share strides");
-  TORCH_CHECK(q.size(2) % 64 == 0, "attention kernel requires T %% 64 == 0");
-  const long long B = q.size(0), H = q.size(1);
-  const int T = q.size(2);
   at::Tensor o = out.has_value() ? *out : at::empty_like(q);
-  check_attn_tensor(o, "o");
-  auto lse = at::empty({B, H, (long long)T}, q.options().dtype(at::kFloat));
-  auto sq = strides3(q);
-  auto so = strides3(o);
-  TORCH_CHECK(dropout_p >= 0.0 && dropout_p < 1.0, "bad dropout_p");
+  check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"out", o, o}},
+                  dropout_p);
+  const long long B = q.size(0), H = q.size(1), T = q.size(2);
+  auto lse = at::empty({B, H, T}, q.options().dtype(at::kFloat));
   check_hip(tdsa_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                          o.data_ptr(), lse.data_ptr<float>(), B, H, T,
-                          (float)scale, sq.data(), so.data(), (float)dropout_p,
-                          (unsigned long long)seed, cur_stream()),
+                          o.data_ptr(), lse.data_ptr<float>(), B, H, (int)T,
+                          (float)scale, strides3(q).data(), strides3(o).data(),
+                          (float)dropout_p, (unsigned long long)seed,
+                          cur_stream()),
             "attention_fwd");
   return {o, lse};
 }
@@ -481,31 +486,24 @@ std::vector<at::Tensor> attention_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                       c10::optional<at::Tensor> dk_out,
                                       c10::optional<at::Tensor> dv_out,
                                       double dropout_p, int64_t seed) {
-  check_attn_tensor(q, "q");
-  check_attn_tensor(k, "k");
-  check_attn_tensor(v, "v");
-  check_attn_tensor(o, "o");
-  check_attn_tensor(dout, "dout");
-  TORCH_CHECK(q.strides() == k.strides() && q.strides() == v.strides(),
-              "q/k/v must share strides");
-  TORCH_CHECK(o.strides() == dout.strides(), "o/dout must share strides");
-  auto lsec = lse.contiguous();
-  const long long B = q.size(0), H = q.size(1);
-  const int T = q.size(2);
   at::Tensor dq = dq_out.has_value() ? *dq_out : at::empty_like(q);
   at::Tensor dk = dk_out.has_value() ? *dk_out : at::empty_like(k);
   at::Tensor dv = dv_out.has_value() ? *dv_out : at::empty_like(v);
-  TORCH_CHECK(dq.strides() == dk.strides() && dq.strides() == dv.strides(),
-              "dq/dk/dv must share strides");
+  check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"o", o, o},
+                   {"dout", dout, o}, {"dq", dq, dq}, {"dk", dk, dq},
+                   {"dv", dv, dq}}, dropout_p);
+  const long long B = q.size(0), H = q.size(1), T = q.size(2);
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
+                  lse.numel() == B * H * T,
+              "lse must be fp32 on GPU with B*H*T elements, got ", lse.sizes());
+  auto lsec = lse.contiguous();
   auto delta = at::empty({B * H * T}, q.options().dtype(at::kFloat));
-  auto sq = strides3(q);
-  auto so = strides3(o);
-  auto sd = strides3(dq);
   check_hip(tdsa_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                           o.data_ptr(), lsec.data_ptr<float>(), dout.data_ptr(),
                           dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                          delta.data_ptr<float>(), B, H, T, (float)scale,
-                          sq.data(), so.data(), sd.data(), (float)dropout_p,
+                          delta.data_ptr<float>(), B, H, (int)T, (float)scale,
+                          strides3(q).data(), strides3(o).data(),
+                          strides3(dq).data(), (float)dropout_p,
                           (unsigned long long)seed, cur_stream()),
             "attention_bwd");
   return {dq, dk, dv};

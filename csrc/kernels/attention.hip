@@ -19,6 +19,10 @@
 //             accumulates dK/dV over 64-row Q tiles, consuming delta.
 //             The 1/sqrt(D) on dS is folded into the dK/dQ epilogue.
 //
+// The three kernels share one skeleton: BlockCtx (block prologue), TilePipe
+// (two-tile LDS pipeline), FragOff (fragment read offsets), frag_from_packed
+// (C -> A repack) and store_ctiles (epilogue).
+//
 // All global accesses are stride-parameterized so the kernels consume the
 // packed qkv projection layout (B,T,3,H,D) and write O/dQKV into (B,T,H,D)
 // buffers directly — no transpose-copies on the hot path.
@@ -39,7 +43,6 @@
 #include "common.h"
 #include "mfma.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace tdsa {
@@ -78,25 +81,109 @@ struct GStride {
   int t;
 };
 
+// Block prologue of all three kernels: the remapped (tile, batch*head) this
+// block owns and the lane's place in its wave's 32x32 MFMA tiles.
+struct BlockCtx {
+  int tile;        // block index along T after the XCD remap
+  long long bh;    // batch * H + head
+  int tid, lane, w;
+  int x32, h32;    // lane % 32 (index on the 32-axis), lane / 32
+
+  DEV_INLINE BlockCtx() {
+    tile = blockIdx.x;
+    bh = blockIdx.y;
+    xcd_remap(gridDim.x, gridDim.y, tile, bh);
+    tid = threadIdx.x;
+    lane = tid & (WAVE - 1);
+    w = tid / WAVE;
+    x32 = lane & 31;
+    h32 = lane >> 5;
+  }
+
+  // element offset of this block's (batch, head) in a tensor with strides s
+  DEV_INLINE long long base(const GStride& s, int H) const {
+    return (bh / H) * s.b + (bh % H) * s.h;
+  }
+};
+
+// Byte offset of this lane's A/B fragment for k-slice s in 32-row half t2 of
+// a swizzled [64][64] image: swz(32*t2 + x32, 2*(16*s + 8*h32)). The s/h
+// term and the swizzle XOR live in the same byte bits 4-6, so XOR composes
+// and the offset is cheap enough to compute at each use: the forward and dkv
+// kernels do, which keeps 8 VGPRs free for their staging split.
+struct FragOff {
+  int row[2];
+  int xk;
+  int h16;
+
+  DEV_INLINE FragOff(const BlockCtx& c)
+      : row{c.x32 * 128, (32 + c.x32) * 128}, xk((c.x32 & 7) << 4),
+        h16(16 * c.h32) {}
+
+  DEV_INLINE int operator()(int t2, int s) const {
+    return row[t2] + ((s * 32 + h16) ^ xk);
+  }
+};
+
+// Two-tile LDS pipeline: a pair of [64][64] tiles is staged per iteration,
+// with the next pair's global loads in flight under this pair's compute.
+//   prime();
+//   for (...) { next(lds_a, lds_b, more); <other LDS fills>; __syncthreads();
+//               <compute on lds_a / lds_b> }
+template <int NT>
+struct TilePipe {
+  Stage<NT> a, b;
+  short8v pend_a[Stage<NT>::REPS], pend_b[Stage<NT>::REPS];
+
+  DEV_INLINE TilePipe(const bf16* ga, int st_a, const bf16* gb, int st_b,
+                      int tid)
+      : a(ga, tid, st_a), b(gb, tid, st_b) {}
+
+  DEV_INLINE void prime() {
+    a.fetch(pend_a);
+    b.fetch(pend_b);
+  }
+
+  // Barrier (the previous pair is consumed), pending registers -> LDS, and
+  // with `more` the loads of the following pair. The caller places the
+  // barrier that publishes the tiles.
+  DEV_INLINE void next(char* lds_a, char* lds_b, bool more) {
+    __syncthreads();
+    a.put(lds_a, pend_a);
+    b.put(lds_b, pend_b);
+    if (more) {
+      a.advance();
+      b.advance();
+      a.fetch(pend_a);
+      b.fetch(pend_b);
+    }
+  }
+};
+
 // Counter-based dropout RNG: keyed by (bh, qrow, key) so the backward
 // kernels REGENERATE the forward's mask from (seed, indices) — nothing is
 // stored, matching the recompute design. 32-bit fold + murmur3 fmix32
 // finalizer: the first splitmix64 version kept 64-bit temporaries live
 // across the softmax loop and pushed the DROP template into a 312 B/lane
 // spill — the avalanche quality of fmix32 is ample for dropout.
-// keep <=> rng < threshold, threshold = (1-p) * 2^32.
-DEV_INLINE bool drop_keep(unsigned long long seed, unsigned long long idx,
-                          unsigned thr) {
-  unsigned h = (unsigned)(idx ^ (idx >> 32));
-  h += (unsigned)seed;
-  h ^= (unsigned)(seed >> 32);
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h < thr;
-}
+// keep <=> rng < keep_thr, keep_thr = (1-p) * 2^32.
+struct Dropout {
+  unsigned long long seed;
+  unsigned keep_thr;
+  float inv_keep;   // 1 / (1-p)
+
+  DEV_INLINE bool keep(unsigned long long idx) const {
+    unsigned h = (unsigned)(idx ^ (idx >> 32));
+    h += (unsigned)seed;
+    h ^= (unsigned)(seed >> 32);
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h < keep_thr;
+  }
+};
 
 // C-layout -> A-fragment repack. Values live per lane as 16 C registers per
 // 32-wide tile (packed to bf16 word pairs wA[r1]=(r0=0,1), wB[r1]=(r0=2,3)).
@@ -108,12 +195,12 @@ struct PackedC {
   unsigned wB[2][4];
 };
 
-template <int S>
-DEV_INLINE bfrag frag_from_packed(const PackedC& p) {
-  const unsigned uA = p.wA[S >> 1][2 * (S & 1)];
-  const unsigned vA = p.wA[S >> 1][2 * (S & 1) + 1];
-  const unsigned uB = p.wB[S >> 1][2 * (S & 1)];
-  const unsigned vB = p.wB[S >> 1][2 * (S & 1) + 1];
+// `s` is a constant once the caller's slice loop is unrolled.
+DEV_INLINE bfrag frag_from_packed(const PackedC& p, int s) {
+  const unsigned uA = p.wA[s >> 1][2 * (s & 1)];
+  const unsigned vA = p.wA[s >> 1][2 * (s & 1) + 1];
+  const unsigned uB = p.wB[s >> 1][2 * (s & 1)];
+  const unsigned vB = p.wB[s >> 1][2 * (s & 1) + 1];
   auto rA = __builtin_amdgcn_permlane32_swap(uA, vA, false, false);
   auto rB = __builtin_amdgcn_permlane32_swap(uB, vB, false, false);
   union { bfrag f; unsigned w[4]; } r;
@@ -139,98 +226,93 @@ DEV_INLINE bfrag load_frag(const bf16* p, int row, int col, int st) {
   return r.f;
 }
 
+// Epilogue of one wave's 32x64 result, held as two C tiles: element
+// (crow(r,h32), 32*dt + x32) = acc[dt][r] * mul(r), stored as bf16 at row
+// stride st from p (the wave's first row).
+template <typename F>
+DEV_INLINE void store_ctiles(bf16* p, int st, const BlockCtx& c,
+                             const f32x16 (&acc)[2], F mul) {
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      p[crow(r, c.h32) * st + dt * 32 + c.x32] = f2bf(acc[dt][r] * mul(r));
+}
+
 // ---------------------------------------------------------------------------
 // Forward
 // ---------------------------------------------------------------------------
-template <int NW, bool DROP = false, int MINW = (NW == 8 ? 4 : 2)>
 // NW=8: cap at 128 VGPR so two 8-wave blocks are resident per CU (at 132
-// VGPR the 8-wave granularity rounds occupancy down to ONE block).
+// VGPR the 8-wave granularity rounds occupancy down to ONE block). With
+// DROP the no-drop kernel's 128 registers are already full and the cap
+// spills 316 B/lane, so dropout takes the relaxed cap (168 VGPR, 1 block/CU),
+// which measured faster for it.
+constexpr int fwd_min_blocks(int nw, bool drop) {
+  return nw == 8 ? (drop ? 3 : 4) : 2;
+}
+
+template <int NW, bool DROP = false>
 // DROP: fused attention dropout — the row sum l_run uses the UNMASKED
 // exponentials (normalization is the true softmax sum) while the PV
 // accumulation consumes masked/rescaled P.
-__launch_bounds__(NW * WAVE, MINW)
+__launch_bounds__(NW * WAVE, fwd_min_blocks(NW, DROP))
 __global__ void attn_fwd_kernel(const bf16* __restrict__ q,
                                 const bf16* __restrict__ k,
                                 const bf16* __restrict__ v,
                                 bf16* __restrict__ o, float* __restrict__ lse,
                                 int T, int H, float scale, GStride sq,
-                                GStride so, unsigned long long seed,
-                                unsigned keep_thr, float inv_keep) {
+                                GStride so, Dropout drop) {
   constexpr int BM = NW * 32;
   constexpr int NT = NW * WAVE;
   __shared__ __attribute__((aligned(16))) char smem[2 * KVB * D * 2];
   char* lds_k = smem;                 // [64][64] keys row-major
   char* lds_v = smem + KVB * D * 2;   // [64][64] values row-major
 
-  int qb = blockIdx.x;
-  long long bh = blockIdx.y;
-  xcd_remap(gridDim.x, gridDim.y, qb, bh);
-  const int tid = threadIdx.x;
-  const int lane = tid & (WAVE - 1);
-  const int w = tid / WAVE;
-  const int q32 = lane & 31;
-  const int h32 = lane >> 5;
+  const BlockCtx c;                   // c.tile: Q block
+  const long long boff = c.base(sq, H);
+  const bf16* qp = q + boff + (long long)(c.tile * BM) * sq.t;
 
-  const long long boff = (bh / H) * sq.b + (bh % H) * sq.h;
-  const bf16* qp = q + boff + (long long)(qb * BM) * sq.t;
-  const bf16* kp = k + boff;
-  const bf16* vp = v + boff;
-
-  Stage<NT> stage_k(kp, tid, sq.t);
-  Stage<NT> stage_v(vp, tid, sq.t);
-  // K fragment offsets on the fly (same bit trick as AF_OFF in dkv)
-  const int kf_row[2] = {q32 * 128, (32 + q32) * 128};
-  const int kf_xk = (q32 & 7) << 4;
-#define KF_OFF(t2, s) (kf_row[t2] + (((s) * 32 + 16 * h32) ^ kf_xk))
+  TilePipe<NT> pipe(k + boff, sq.t, v + boff, sq.t, c.tid);
+  const FragOff kf(c);
   int trb[2][2];
-  tr_bases(lane, trb);
+  tr_bases(c.lane, trb);
   const float qscale = scale * LOG2E;
   bfrag q_frag[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s)
-    q_frag[s] = load_frag_scaled(qp, w * 32 + q32, s * 16 + 8 * h32, sq.t,
-                                 qscale);
+    q_frag[s] = load_frag_scaled(qp, c.w * 32 + c.x32, s * 16 + 8 * c.h32,
+                                 sq.t, qscale);
 
   const f32x16 kzero = {};
   f32x16 o_acc[2] = {};
   float m_run = -INFINITY;
   float l_run = 0.f;
 
-  const int row_lo = qb * BM + w * 32;
-  const int row_me = row_lo + q32;
+  const int row_lo = c.tile * BM + c.w * 32;
+  const int row_me = row_lo + c.x32;
   // dropout index base (loop-invariant): idx = base + key
   const unsigned long long drop_base =
-      DROP ? ((unsigned long long)bh * T + row_me) * T : 0;
-  const int n_kv = (qb + 1) * BM / KVB;
-  short8v pend_k[Stage<NT>::REPS], pend_v[Stage<NT>::REPS];
-  stage_k.fetch(pend_k);
-  stage_v.fetch(pend_v);
+      DROP ? ((unsigned long long)c.bh * T + row_me) * T : 0;
+  const int n_kv = (c.tile + 1) * BM / KVB;
+  pipe.prime();
   for (int j = 0; j < n_kv; ++j) {
-    __syncthreads();
-    stage_k.put(lds_k, pend_k);
-    stage_v.put(lds_v, pend_v);
-    if (j + 1 < n_kv) {
-      stage_k.advance();
-      stage_v.advance();
-      stage_k.fetch(pend_k);
-      stage_v.fetch(pend_v);
-    }
+    pipe.next(lds_k, lds_v, j + 1 < n_kv);
     __syncthreads();
 
     const int key0 = j * KVB;
     if (key0 > row_lo + 31) continue;
 
-    // S^T tiles: C[key = 32*t2 + crow(r,h32)][qrow = q32], log2-scaled
+    // S^T tiles: C[key = 32*t2 + crow(r,h32)][qrow = x32], log2-scaled
     f32x16 st[2];
     __builtin_amdgcn_s_setprio(1);  // favor MFMA-issuing waves (T5)
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {
       // seed from the loop-invariant zero vector: a per-tile `= {}` init
       // re-emits 16 v_mov per accumulator per tile
-      f32x16 acc = MFMA32(lds_read16(lds_k, KF_OFF(t2, 0)), q_frag[0], kzero);
+      f32x16 acc = MFMA32(lds_read16(lds_k, kf(t2, 0)), q_frag[0], kzero);
 #pragma unroll
       for (int s = 1; s < 4; ++s)
-        acc = MFMA32(lds_read16(lds_k, KF_OFF(t2, s)), q_frag[s], acc);
+        acc = MFMA32(lds_read16(lds_k, kf(t2, s)), q_frag[s], acc);
       st[t2] = acc;
     }
     __builtin_amdgcn_s_setprio(0);
@@ -242,7 +324,7 @@ __global__ void attn_fwd_kernel(const bf16* __restrict__ q,
       for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = key0 + t2 * 32 + crow(r, h32);
+          const int key = key0 + t2 * 32 + crow(r, c.h32);
           float s = (key <= row_me) ? st[t2][r] : -INFINITY;
           st[t2][r] = s;
           mt = fmaxf(mt, s);
@@ -268,10 +350,8 @@ __global__ void attn_fwd_kernel(const bf16* __restrict__ q,
           float pe = fast_exp2(st[t2][4 * r1 + e] - m_new);
           psum += pe;
           if (DROP) {
-            const int key = key0 + t2 * 32 + crow(4 * r1 + e, h32);
-            pe = drop_keep(seed, drop_base + key, keep_thr)
-                     ? pe * inv_keep
-                     : 0.f;
+            const int key = key0 + t2 * 32 + crow(4 * r1 + e, c.h32);
+            pe = drop.keep(drop_base + key) ? pe * drop.inv_keep : 0.f;
           }
           p[e] = pe;
         }
@@ -286,7 +366,7 @@ __global__ void attn_fwd_kernel(const bf16* __restrict__ q,
       float a_row[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        a_row[r] = __shfl(alpha, crow(r, h32), WAVE);
+        a_row[r] = __shfl(alpha, crow(r, c.h32), WAVE);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -297,13 +377,7 @@ __global__ void attn_fwd_kernel(const bf16* __restrict__ q,
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      bfrag pa;
-      switch (s) {
-        case 0: pa = frag_from_packed<0>(P); break;
-        case 1: pa = frag_from_packed<1>(P); break;
-        case 2: pa = frag_from_packed<2>(P); break;
-        default: pa = frag_from_packed<3>(P); break;
-      }
+      const bfrag pa = frag_from_packed(P, s);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
         o_acc[dt] = MFMA32(pa, tr_bfrag(lds_v, trb[dt][0] + s * 2048,
@@ -316,17 +390,11 @@ __global__ void attn_fwd_kernel(const bf16* __restrict__ q,
   float linv_row[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r)
-    linv_row[r] = fast_rcp(__shfl(l_run, crow(r, h32), WAVE));
-  bf16* op = o + (bh / H) * so.b + (bh % H) * so.h
-             + (long long)(qb * BM + w * 32) * so.t;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      op[crow(r, h32) * so.t + dt * 32 + q32] =
-          f2bf(o_acc[dt][r] * linv_row[r]);
-  if (lane < 32) {
-    lse[bh * T + qb * BM + w * 32 + q32] = (m_run + log2f(l_run)) * LN2;
+    linv_row[r] = fast_rcp(__shfl(l_run, crow(r, c.h32), WAVE));
+  store_ctiles(o + c.base(so, H) + (long long)row_lo * so.t, so.t, c, o_acc,
+               [&](int r) { return linv_row[r]; });
+  if (c.lane < 32) {
+    lse[c.bh * T + row_me] = (m_run + log2f(l_run)) * LN2;
   }
 }
 
@@ -346,9 +414,7 @@ __global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
                                     const float* __restrict__ delta,
                                     bf16* __restrict__ dk, bf16* __restrict__ dv,
                                     int T, int H, float scale, GStride sq,
-                                    GStride so, GStride sd,
-                                    unsigned long long seed, unsigned keep_thr,
-                                    float inv_keep) {
+                                    GStride so, GStride sd, Dropout drop) {
   constexpr int BK = NW * 32;
   constexpr int NT = NW * WAVE;
   __shared__ __attribute__((aligned(16))) char smem[2 * KVB * D * 2 + 2 * KVB * 4];
@@ -357,67 +423,40 @@ __global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
   float* lds_lse = reinterpret_cast<float*>(smem + 2 * KVB * D * 2);
   float* lds_dlt = lds_lse + KVB;
 
-  int jb = blockIdx.x;
-  long long bh = blockIdx.y;
-  xcd_remap(gridDim.x, gridDim.y, jb, bh);
-  const int tid = threadIdx.x;
-  const int lane = tid & (WAVE - 1);
-  const int w = tid / WAVE;
-  const int k32 = lane & 31;   // this lane's key within the wave tile
-  const int h32 = lane >> 5;
+  const BlockCtx c;                   // c.tile: key block, c.x32: key in wave
+  const long long boff = c.base(sq, H);
+  const int i0 = c.tile * BK / KVB;   // first Q tile that sees these keys
 
-  const long long boff = (bh / H) * sq.b + (bh % H) * sq.h;
-  const long long ooff = (bh / H) * so.b + (bh % H) * so.h;
-  const bf16* qp = q + boff;
-  const bf16* kp = k + boff;
-  const bf16* vp = v + boff;
-  const bf16* dop = dout + ooff;
-
-  Stage<NT> stage_q(qp + (long long)(jb * BK / KVB * KVB) * sq.t, tid, sq.t);
-  Stage<NT> stage_do(dop + (long long)(jb * BK / KVB * KVB) * so.t, tid, so.t);
-  // fragment offsets on the fly: af(t2, s) = rowbase[t2] + (s-term ^ xk);
-  // the s/h term and the swizzle XOR live in the same byte bits 4-6, so XOR
-  // composes (keeps 8 VGPRs free for the staging split below)
-  const int af_row[2] = {k32 * 128, (32 + k32) * 128};
-  const int af_xk = (k32 & 7) << 4;
-#define AF_OFF(t2, s) (af_row[t2] + (((s) * 32 + 16 * h32) ^ af_xk))
+  TilePipe<NT> pipe(q + boff + (long long)(i0 * KVB) * sq.t, sq.t,
+                    dout + c.base(so, H) + (long long)(i0 * KVB) * so.t, so.t,
+                    c.tid);
+  const FragOff af(c);
   int trb[2][2];
-  tr_bases(lane, trb);
+  tr_bases(c.lane, trb);
   const float kscale = scale * LOG2E;
-  const int key_lo = jb * BK + w * 32;
-  const int key_me = key_lo + k32;
+  const int key_lo = c.tile * BK + c.w * 32;
+  const int key_me = key_lo + c.x32;
   // dropout index base: idx = base + qrow*T + key_me (qrow*T fits 32 bits)
   const unsigned long long drop_bhTT =
-      DROP ? (unsigned long long)bh * T * T : 0;
-  bfrag k_frag[4], v_frag[4];  // B operands: col = k32, k-slices over D
+      DROP ? (unsigned long long)c.bh * T * T : 0;
+  bfrag k_frag[4], v_frag[4];  // B operands: col = x32, k-slices over D
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    k_frag[s] = load_frag_scaled(kp, key_lo + k32, s * 16 + 8 * h32, sq.t,
+    k_frag[s] = load_frag_scaled(k + boff, key_me, s * 16 + 8 * c.h32, sq.t,
                                  kscale);
-    v_frag[s] = load_frag(vp, key_lo + k32, s * 16 + 8 * h32, sq.t);
+    v_frag[s] = load_frag(v + boff, key_me, s * 16 + 8 * c.h32, sq.t);
   }
 
   const f32x16 kzero = {};
   f32x16 dk_acc[2] = {};
   f32x16 dv_acc[2] = {};
 
-  const int i0 = jb * BK / KVB;
-  short8v pend_q[Stage<NT>::REPS], pend_do[Stage<NT>::REPS];
-  stage_q.fetch(pend_q);
-  stage_do.fetch(pend_do);
+  pipe.prime();
   for (int i = i0; i < T / KVB; ++i) {
-    __syncthreads();
-    stage_q.put(lds_q, pend_q);
-    stage_do.put(lds_do, pend_do);
-    if (i + 1 < T / KVB) {
-      stage_q.advance();
-      stage_do.advance();
-      stage_q.fetch(pend_q);   // next tile flies under this tile's compute
-      stage_do.fetch(pend_do);
-    }
-    if (tid < KVB) {
-      lds_lse[tid] = lse[bh * T + i * KVB + tid] * LOG2E;
-      lds_dlt[tid] = delta[bh * T + i * KVB + tid];
+    pipe.next(lds_q, lds_do, i + 1 < T / KVB);
+    if (c.tid < KVB) {
+      lds_lse[c.tid] = lse[c.bh * T + i * KVB + c.tid] * LOG2E;
+      lds_dlt[c.tid] = delta[c.bh * T + i * KVB + c.tid];
     }
     __syncthreads();
 
@@ -428,14 +467,14 @@ __global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
     PackedC P, dS;
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {
-      // S, dP tiles: C[qrow = 32*t2 + crow(r,h32)][key = k32]
+      // S, dP tiles: C[qrow = 32*t2 + crow(r,h32)][key = x32]
       __builtin_amdgcn_s_setprio(1);
-      f32x16 s_acc = MFMA32(lds_read16(lds_q, AF_OFF(t2, 0)), k_frag[0], kzero);
-      f32x16 dp_acc = MFMA32(lds_read16(lds_do, AF_OFF(t2, 0)), v_frag[0], kzero);
+      f32x16 s_acc = MFMA32(lds_read16(lds_q, af(t2, 0)), k_frag[0], kzero);
+      f32x16 dp_acc = MFMA32(lds_read16(lds_do, af(t2, 0)), v_frag[0], kzero);
 #pragma unroll
       for (int s = 1; s < 4; ++s) {
-        s_acc = MFMA32(lds_read16(lds_q, AF_OFF(t2, s)), k_frag[s], s_acc);
-        dp_acc = MFMA32(lds_read16(lds_do, AF_OFF(t2, s)), v_frag[s], dp_acc);
+        s_acc = MFMA32(lds_read16(lds_q, af(t2, s)), k_frag[s], s_acc);
+        dp_acc = MFMA32(lds_read16(lds_do, af(t2, s)), v_frag[s], dp_acc);
       }
       __builtin_amdgcn_s_setprio(0);
       // MASK as a compile-time split: `diag` is wave-uniform but inside the
@@ -449,18 +488,16 @@ __global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int r = 4 * r1 + e;
-            const int lrow = t2 * 32 + crow(r, h32);
+            const int lrow = t2 * 32 + crow(r, c.h32);
             float pp = fast_exp2(s_acc[r] - lds_lse[lrow]);
             if (MASK.value) pp = (key_me <= q0 + lrow) ? pp : 0.f;
             float pv = pp;                 // masked/rescaled P feeds dV
             float dpv = dp_acc[r];         // masked/rescaled dP feeds dS
             if (DROP) {
-              const bool keep = drop_keep(
-                  seed,
-                  drop_bhTT + (unsigned)((q0 + lrow) * T) + key_me,
-                  keep_thr);
-              pv = keep ? pp * inv_keep : 0.f;
-              dpv = keep ? dpv * inv_keep : 0.f;
+              const bool keep = drop.keep(
+                  drop_bhTT + (unsigned)((q0 + lrow) * T) + key_me);
+              pv = keep ? pp * drop.inv_keep : 0.f;
+              dpv = keep ? dpv * drop.inv_keep : 0.f;
             }
             p[e] = pv;
             dsv[e] = pp * (dpv - lds_dlt[lrow]);  // scale in epilogue
@@ -481,13 +518,8 @@ __global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      bfrag ap, as;
-      switch (s) {
-        case 0: ap = frag_from_packed<0>(P); as = frag_from_packed<0>(dS); break;
-        case 1: ap = frag_from_packed<1>(P); as = frag_from_packed<1>(dS); break;
-        case 2: ap = frag_from_packed<2>(P); as = frag_from_packed<2>(dS); break;
-        default: ap = frag_from_packed<3>(P); as = frag_from_packed<3>(dS); break;
-      }
+      const bfrag ap = frag_from_packed(P, s);
+      const bfrag as = frag_from_packed(dS, s);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
         dv_acc[dt] = MFMA32(ap, tr_bfrag(lds_do, trb[dt][0] + s * 2048,
@@ -501,16 +533,17 @@ __global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
     __builtin_amdgcn_s_setprio(0);
   }
 
-  const long long doff = (bh / H) * sd.b + (bh % H) * sd.h
-                         + (long long)(key_lo) * sd.t;
+  // dk and dv stores interleaved (not two store_ctiles passes): the order
+  // the epilogue was measured with
+  const long long doff = c.base(sd, H) + (long long)(key_lo) * sd.t;
   bf16* dkp = dk + doff;
   bf16* dvp = dv + doff;
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      dkp[crow(r, h32) * sd.t + dt * 32 + k32] = f2bf(dk_acc[dt][r] * scale);
-      dvp[crow(r, h32) * sd.t + dt * 32 + k32] = f2bf(dv_acc[dt][r]);
+      dkp[crow(r, c.h32) * sd.t + dt * 32 + c.x32] = f2bf(dk_acc[dt][r] * scale);
+      dvp[crow(r, c.h32) * sd.t + dt * 32 + c.x32] = f2bf(dv_acc[dt][r]);
     }
 }
 
@@ -528,53 +561,41 @@ __global__ void attn_bwd_dq_kernel(const bf16* __restrict__ q,
                                    float* __restrict__ delta,
                                    bf16* __restrict__ dq, int T, int H,
                                    float scale, GStride sq, GStride so,
-                                   GStride sd, unsigned long long seed,
-                                   unsigned keep_thr, float inv_keep) {
+                                   GStride sd, Dropout drop) {
   constexpr int BM = NW * 32;
   constexpr int NT = NW * WAVE;
   __shared__ __attribute__((aligned(16))) char smem[2 * KVB * D * 2];
   char* lds_k = smem;                     // K row-major
   char* lds_v = smem + KVB * D * 2;       // V row-major
 
-  int qb = blockIdx.x;
-  long long bh = blockIdx.y;
-  xcd_remap(gridDim.x, gridDim.y, qb, bh);
-  const int tid = threadIdx.x;
-  const int lane = tid & (WAVE - 1);
-  const int w = tid / WAVE;
-  const int q32 = lane & 31;
-  const int h32 = lane >> 5;
+  const BlockCtx c;                       // c.tile: Q block
+  const long long boff = c.base(sq, H);
+  const long long ooff = c.base(so, H) + (long long)(c.tile * BM) * so.t;
+  const bf16* qp = q + boff + (long long)(c.tile * BM) * sq.t;
 
-  const long long boff = (bh / H) * sq.b + (bh % H) * sq.h;
-  const long long ooff = (bh / H) * so.b + (bh % H) * so.h;
-  const bf16* qp = q + boff + (long long)(qb * BM) * sq.t;
-  const bf16* kp = k + boff;
-  const bf16* vp = v + boff;
-  const bf16* dop = dout + ooff + (long long)(qb * BM) * so.t;
-
-  Stage<NT> stage_k(kp, tid, sq.t);
-  Stage<NT> stage_v(vp, tid, sq.t);
-  int f_off[2][4];
+  TilePipe<NT> pipe(k + boff, sq.t, v + boff, sq.t, c.tid);
+  const FragOff fo(c);
+  int f_off[2][4];   // kept in registers here: this kernel has them to spare
 #pragma unroll
   for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
-    for (int s = 0; s < 4; ++s)
-      f_off[t2][s] = swz(t2 * 32 + q32, (s * 16 + 8 * h32) * 2);
+    for (int s = 0; s < 4; ++s) f_off[t2][s] = fo(t2, s);
   int trb[2][2];
-  tr_bases(lane, trb);
+  tr_bases(c.lane, trb);
   const float qscale = scale * LOG2E;
   bfrag q_frag[4], do_frag[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    q_frag[s] = load_frag_scaled(qp, w * 32 + q32, s * 16 + 8 * h32, sq.t,
-                                 qscale);
-    do_frag[s] = load_frag(dop, w * 32 + q32, s * 16 + 8 * h32, so.t);
+    q_frag[s] = load_frag_scaled(qp, c.w * 32 + c.x32, s * 16 + 8 * c.h32,
+                                 sq.t, qscale);
+    do_frag[s] = load_frag(dout + ooff, c.w * 32 + c.x32, s * 16 + 8 * c.h32,
+                           so.t);
   }
-  const int row_lo = qb * BM + w * 32;
-  const int row_me = row_lo + q32;
+  const int row_lo = c.tile * BM + c.w * 32;
+  const int row_me = row_lo + c.x32;
   const unsigned long long drop_base =
-      DROP ? ((unsigned long long)bh * T + row_me) * T : 0;
-  const float lse2_me = lse[bh * T + row_me] * LOG2E;
+      DROP ? ((unsigned long long)c.bh * T + row_me) * T : 0;
+  const float lse2_me = lse[c.bh * T + row_me] * LOG2E;
   // delta = rowsum(dO*O) computed here from the fragments already in
   // registers (+ one O load) and PUBLISHED for the dkv kernel, which is
   // launched after this one — replaces a separate full-pass delta kernel.
@@ -582,8 +603,7 @@ __global__ void attn_bwd_dq_kernel(const bf16* __restrict__ q,
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     union { bfrag f; short8v v8; } ov;
-    ov.f = load_frag(o + ooff + (long long)(qb * BM) * so.t, w * 32 + q32,
-                     s * 16 + 8 * h32, so.t);
+    ov.f = load_frag(o + ooff, c.w * 32 + c.x32, s * 16 + 8 * c.h32, so.t);
     union { bfrag f; short8v v8; } dv;
     dv.f = do_frag[s];
 #pragma unroll
@@ -591,25 +611,15 @@ __global__ void attn_bwd_dq_kernel(const bf16* __restrict__ q,
       dlt_me += bf_elem(ov.v8, e) * bf_elem(dv.v8, e);
   }
   dlt_me += __shfl_xor(dlt_me, 32, WAVE);
-  if (lane < 32) delta[bh * T + row_me] = dlt_me;
+  if (c.lane < 32) delta[c.bh * T + row_me] = dlt_me;
 
   const f32x16 kzero = {};
   f32x16 dq_acc[2] = {};
 
-  const int n_kv = (qb + 1) * BM / KVB;
-  short8v pend_k[Stage<NT>::REPS], pend_v[Stage<NT>::REPS];
-  stage_k.fetch(pend_k);
-  stage_v.fetch(pend_v);
+  const int n_kv = (c.tile + 1) * BM / KVB;
+  pipe.prime();
   for (int j = 0; j < n_kv; ++j) {
-    __syncthreads();
-    stage_k.put(lds_k, pend_k);
-    stage_v.put(lds_v, pend_v);
-    if (j + 1 < n_kv) {
-      stage_k.advance();
-      stage_v.advance();
-      stage_k.fetch(pend_k);   // next tile flies under this tile's compute
-      stage_v.fetch(pend_v);
-    }
+    pipe.next(lds_k, lds_v, j + 1 < n_kv);
     __syncthreads();
 
     const int key0 = j * KVB;
@@ -619,7 +629,7 @@ __global__ void attn_bwd_dq_kernel(const bf16* __restrict__ q,
     PackedC dS;
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {
-      // S^T, dP^T tiles: C[key = 32*t2 + crow(r,h32)][qrow = q32]
+      // S^T, dP^T tiles: C[key = 32*t2 + crow(r,h32)][qrow = x32]
       __builtin_amdgcn_s_setprio(1);
       f32x16 s_acc = MFMA32(lds_read16(lds_k, f_off[t2][0]), q_frag[0], kzero);
       f32x16 dp_acc = MFMA32(lds_read16(lds_v, f_off[t2][0]), do_frag[0], kzero);
@@ -636,15 +646,13 @@ __global__ void attn_bwd_dq_kernel(const bf16* __restrict__ q,
         for (int r = 0; r < 16; ++r) {
           float pp = fast_exp2(s_acc[r] - lse2_me);
           if (MASK.value) {
-            const int key = key0 + t2 * 32 + crow(r, h32);
+            const int key = key0 + t2 * 32 + crow(r, c.h32);
             pp = (key <= row_me) ? pp : 0.f;
           }
           float dpv = dp_acc[r];
           if (DROP) {
-            const int key = key0 + t2 * 32 + crow(r, h32);
-            dpv = drop_keep(seed, drop_base + key, keep_thr)
-                      ? dpv * inv_keep
-                      : 0.f;
+            const int key = key0 + t2 * 32 + crow(r, c.h32);
+            dpv = drop.keep(drop_base + key) ? dpv * drop.inv_keep : 0.f;
           }
           dsv[r] = pp * (dpv - dlt_me);
         }
@@ -664,13 +672,7 @@ __global__ void attn_bwd_dq_kernel(const bf16* __restrict__ q,
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      bfrag as;
-      switch (s) {
-        case 0: as = frag_from_packed<0>(dS); break;
-        case 1: as = frag_from_packed<1>(dS); break;
-        case 2: as = frag_from_packed<2>(dS); break;
-        default: as = frag_from_packed<3>(dS); break;
-      }
+      const bfrag as = frag_from_packed(dS, s);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
         dq_acc[dt] = MFMA32(as, tr_bfrag(lds_k, trb[dt][0] + s * 2048,
@@ -680,13 +682,41 @@ __global__ void attn_bwd_dq_kernel(const bf16* __restrict__ q,
     __builtin_amdgcn_s_setprio(0);
   }
 
-  bf16* dqp = dq + (bh / H) * sd.b + (bh % H) * sd.h
-              + (long long)(qb * BM + w * 32) * sd.t;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      dqp[crow(r, h32) * sd.t + dt * 32 + q32] = f2bf(dq_acc[dt][r] * scale);
+  store_ctiles(dq + c.base(sd, H) + (long long)row_lo * sd.t, sd.t, c, dq_acc,
+               [&](int) { return scale; });
+}
+
+// ---------------------------------------------------------------------------
+// Host side
+// ---------------------------------------------------------------------------
+static GStride gstride(const long long* s) { return {s[0], s[1], (int)s[2]}; }
+
+static Dropout make_dropout(float p, unsigned long long seed) {
+  const double keepd = 1.0 - (double)p;
+  // clamp: for p -> 0, keepd*2^32 == 2^32 overflows (unsigned) to 0 and
+  // would drop EVERYTHING instead of nothing
+  const double thr_d = keepd * 4294967296.0;
+  const unsigned keep_thr =
+      thr_d >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)thr_d;
+  return {seed, keep_thr, (float)(1.0 / keepd)};
+}
+
+// Calls f(NW, DROP) as std::integral_constants. NW is the widest block that
+// divides T, capped by the knob `nw_env` (2, 4 or 8, anything else counts as
+// the default 8; read at every launch — within-box A/B, because box-to-box
+// wall-clock noise is ~3%). 8-wave blocks are the measured best: backward
+// 285us vs 332us for 4-wave at B8/H16/T1024 (pre-tr16), staging
+// amortization across 8 waves beat block overlap.
+template <typename F>
+static void attn_dispatch(int T, const char* nw_env, bool drop, F f) {
+  const long long knob = env_int(nw_env, 8);
+  const int nw_max = (knob == 2 || knob == 4) ? (int)knob : 8;
+  auto with_nw = [&](auto DROP) {
+    if (T % 256 == 0 && nw_max == 8) f(std::integral_constant<int, 8>{}, DROP);
+    else if (T % 128 == 0 && nw_max >= 4) f(std::integral_constant<int, 4>{}, DROP);
+    else f(std::integral_constant<int, 2>{}, DROP);
+  };
+  if (drop) with_nw(std::true_type{}); else with_nw(std::false_type{});
 }
 
 }  // namespace tdsa
@@ -694,15 +724,6 @@ __global__ void attn_bwd_dq_kernel(const bf16* __restrict__ q,
 using namespace tdsa;
 
 extern "C" {
-
-// Within-box tuning knobs (defaults are the measured-best dispatch; the env
-// override exists for A/B because box-to-box wall-clock noise is ~3%).
-static int env_nw(const char* name, int dflt) {
-  const char* v = getenv(name);
-  if (!v) return dflt;
-  int n = atoi(v);
-  return (n == 2 || n == 4 || n == 8) ? n : dflt;
-}
 
 // strides arrays: {b, h, t} in elements, per tensor group:
 // sq = q/k/v, so = o (and dO in bwd), sd = dq/dk/dv.
@@ -714,44 +735,15 @@ hipError_t tdsa_attn_fwd(const void* q, const void* k, const void* v, void* o,
                          const long long* so_in, float dropout_p,
                          unsigned long long seed, hipStream_t stream) {
   if (T % KVB) return hipErrorInvalidValue;
-  GStride sq{sq_in[0], sq_in[1], (int)sq_in[2]};
-  GStride so{so_in[0], so_in[1], (int)so_in[2]};
-  const bool drop = dropout_p > 0.0f;
-  const double keepd = 1.0 - (double)dropout_p;
-  // clamp: for p -> 0, keepd*2^32 == 2^32 overflows (unsigned) to 0 and
-  // would drop EVERYTHING instead of nothing
-  const double thr_d = keepd * 4294967296.0;
-  const unsigned keep_thr =
-      thr_d >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)thr_d;
-  const float inv_keep = (float)(1.0 / keepd);
-#define LAUNCH_FWD(NW, MINW)                                                  \
-  do {                                                                        \
-    if (drop)                                                                 \
-      hipLaunchKernelGGL((attn_fwd_kernel<NW, true, MINW>),                   \
-                         dim3(T / (NW * 32), B * H), dim3(NW * WAVE), 0,      \
-                         stream, (const bf16*)q, (const bf16*)k,              \
-                         (const bf16*)v, (bf16*)o, lse, T, (int)H, scale,     \
-                         sq, so, seed, keep_thr, inv_keep);                   \
-    else                                                                      \
-      hipLaunchKernelGGL((attn_fwd_kernel<NW, false, MINW>),                  \
-                         dim3(T / (NW * 32), B * H), dim3(NW * WAVE), 0,      \
-                         stream, (const bf16*)q, (const bf16*)k,              \
-                         (const bf16*)v, (bf16*)o, lse, T, (int)H, scale,     \
-                         sq, so, seed, keep_thr, inv_keep);                   \
-  } while (0)
-  const int nw_fwd = env_nw("TDSA_ATTN_FWD_NW", 8);
-  const char* mv = getenv("TDSA_ATTN_FWD_MINW");
-  const bool relaxed = (mv && atoi(mv) == 3) || drop;
-  // dropout: the no-drop kernel already fills the 128-VGPR cap, so the
-  // DROP variant spills 316 B/lane under MINW=4 — the relaxed cap
-  // (168 VGPR, 1 block/CU) measured faster for it
-  if (T % 256 == 0 && nw_fwd == 8) {
-    if (relaxed) LAUNCH_FWD(8, 3);  // A/B: no 128-cap spill, 1 block/CU
-    else LAUNCH_FWD(8, 4);
-  }
-  else if (T % 128 == 0 && nw_fwd >= 4) LAUNCH_FWD(4, 2);
-  else LAUNCH_FWD(2, 2);
-#undef LAUNCH_FWD
+  const GStride sq = gstride(sq_in), so = gstride(so_in);
+  const Dropout drop = make_dropout(dropout_p, seed);
+  attn_dispatch(T, "TDSA_ATTN_FWD_NW", dropout_p > 0.0f, [&](auto nw, auto dr) {
+    constexpr int NW = decltype(nw)::value;
+    hipLaunchKernelGGL((attn_fwd_kernel<NW, decltype(dr)::value>),
+                       dim3(T / (NW * 32), B * H), dim3(NW * WAVE), 0, stream,
+                       (const bf16*)q, (const bf16*)k, (const bf16*)v,
+                       (bf16*)o, lse, T, (int)H, scale, sq, so, drop);
+  });
   return hipGetLastError();
 }
 
@@ -763,46 +755,23 @@ hipError_t tdsa_attn_bwd(const void* q, const void* k, const void* v,
                          const long long* sd_in, float dropout_p,
                          unsigned long long seed, hipStream_t stream) {
   if (T % KVB) return hipErrorInvalidValue;
-  GStride sq{sq_in[0], sq_in[1], (int)sq_in[2]};
-  GStride so{so_in[0], so_in[1], (int)so_in[2]};
-  GStride sd{sd_in[0], sd_in[1], (int)sd_in[2]};
-  const long long BH = B * H;
-  const bool drop = dropout_p > 0.0f;
-  const double keepd = 1.0 - (double)dropout_p;
-  // clamp: for p -> 0, keepd*2^32 == 2^32 overflows (unsigned) to 0 and
-  // would drop EVERYTHING instead of nothing
-  const double thr_d = keepd * 4294967296.0;
-  const unsigned keep_thr =
-      thr_d >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)thr_d;
-  const float inv_keep = (float)(1.0 / keepd);
+  const GStride sq = gstride(sq_in), so = gstride(so_in), sd = gstride(sd_in);
+  const Dropout drop = make_dropout(dropout_p, seed);
   // dq runs FIRST: it computes and publishes delta = rowsum(dO*O) from
   // fragments it loads anyway; dkv (same stream) consumes it.
-#define LAUNCH_BWD_D(NW, DR)                                                  \
-  do {                                                                        \
-    dim3 grid(T / (NW * 32), BH);                                             \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<NW, DR>), grid, dim3(NW * WAVE),   \
-                       0, stream, (const bf16*)q, (const bf16*)k,             \
-                       (const bf16*)v, (const bf16*)o, (const bf16*)dout,     \
-                       lse, delta, (bf16*)dq, T, (int)H, scale, sq, so, sd,   \
-                       seed, keep_thr, inv_keep);                             \
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<NW, DR>), grid, dim3(NW * WAVE),  \
-                       0, stream, (const bf16*)q, (const bf16*)k,             \
-                       (const bf16*)v, (const bf16*)dout, lse, delta,         \
-                       (bf16*)dk, (bf16*)dv, T, (int)H, scale, sq, so, sd,    \
-                       seed, keep_thr, inv_keep);                             \
-  } while (0)
-#define LAUNCH_BWD(NW)                                                        \
-  do {                                                                        \
-    if (drop) LAUNCH_BWD_D(NW, true);                                         \
-    else LAUNCH_BWD_D(NW, false);                                             \
-  } while (0)
-  // 8-wave blocks measured 285us vs 332us for 4-wave at B8/H16/T1024
-  // (pre-tr16); staging amortization across 8 waves beat block overlap.
-  const int nw_bwd = env_nw("TDSA_ATTN_BWD_NW", 8);
-  if (T % 256 == 0 && nw_bwd == 8) LAUNCH_BWD(8);
-  else if (T % 128 == 0 && nw_bwd >= 4) LAUNCH_BWD(4);
-  else LAUNCH_BWD(2);
-#undef LAUNCH_BWD
+  attn_dispatch(T, "TDSA_ATTN_BWD_NW", dropout_p > 0.0f, [&](auto nw, auto dr) {
+    constexpr int NW = decltype(nw)::value;
+    constexpr bool DROP = decltype(dr)::value;
+    const dim3 grid(T / (NW * 32), B * H), block(NW * WAVE);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<NW, DROP>), grid, block, 0, stream,
+                       (const bf16*)q, (const bf16*)k, (const bf16*)v,
+                       (const bf16*)o, (const bf16*)dout, lse, delta,
+                       (bf16*)dq, T, (int)H, scale, sq, so, sd, drop);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<NW, DROP>), grid, block, 0, stream,
+                       (const bf16*)q, (const bf16*)k, (const bf16*)v,
+                       (const bf16*)dout, lse, delta, (bf16*)dk, (bf16*)dv, T,
+                       (int)H, scale, sq, so, sd, drop);
+  });
   return hipGetLastError();
 }
 

@@ -213,3 +213,48 @@ def test_attention_rescale_spike_backward_gpu():
     tile. Forward and, new here, dq/dk/dv."""
     case = _case(1, 2, 256, spike=True)
     _check(case, _kernel(*case[0]), "attn spike T256")
+
+
+def test_attention_binding_rejects_wrong_buffers_gpu():
+    """The binding names the argument it rejects instead of launching with
+    another tensor's strides and extents. Every wrong buffer is at least as
+    large as the right one. A valid call after the rejected ones repeats the
+    call made before them bit for bit."""
+    ext = _ext.get_ext()
+    B, H, T = 1, 2, 64
+    q, k, v, do = KC.attn_inputs(B, H, T, "cuda", seed=T + H)
+    before = _kernel(q, k, v, do)
+    o, lse = before[:2]
+
+    def bwd(**wrong):
+        kw = dict(q=q, k=k, v=v, o=o, lse=lse, dout=do, scale=SCALE,
+                  dq=_nan(B, H, T, 64), dk=_nan(B, H, T, 64),
+                  dv=_nan(B, H, T, 64))
+        kw.update(wrong)
+        return ext.attention_bwd(**kw)
+
+    def bwd_t96():
+        t96 = [_nan(B, H, 96, 64).zero_() for _ in range(8)]
+        lse96 = torch.zeros(B, H, 96, device="cuda")
+        return ext.attention_bwd(*t96[:4], lse96, t96[4], SCALE, *t96[5:])
+
+    rejected = [
+        (r"out must have q's sizes",
+         lambda: ext.attention_fwd(q, k, v, SCALE, _nan(B, H, 128, 64))),
+        (r"dq must be bf16", lambda: bwd(dq=_nan(B, H, T, 64).float())),
+        (r"dk last dim must be contiguous",
+         lambda: bwd(dk=_nan(B, H, T, 128)[..., ::2])),
+        (r"dv must have q's sizes", lambda: bwd(dv=_nan(B, 3, T, 64))),
+        (r"lse must be fp32 on GPU with B\*H\*T elements",
+         lambda: bwd(lse=torch.zeros(B, H, 65, device="cuda"))),
+        (r"requires T % 64 == 0", bwd_t96),
+        (r"bad dropout_p", lambda: bwd(dropout_p=1.0)),
+    ]
+    for message, call in rejected:
+        with pytest.raises(RuntimeError, match=message):
+            call()
+
+    after = _kernel(q, k, v, do)
+    for name, a, b in zip(("o", "lse") + GRADS, before, after):
+        assert torch.isfinite(a.float()).all(), name
+        assert torch.equal(a, b), name

@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from tiny_deepspeed_amd import ops
+from tiny_deepspeed_amd.ops import attention as attn_ops
 
 
 def test_linear_ops_match_autograd():
@@ -174,3 +175,111 @@ def test_model_math_and_fused_backends_agree():
     _, lf = m_f(x, y)
     _, lm = m_m(x, y)
     assert torch.allclose(lf, lm, atol=1e-5), (lf.item(), lm.item())
+
+
+class _CompositeAttnExt:
+    """Stands in for the extension on CPU: the two attention entry points,
+    computed by the composite, recording the dropout arguments they get."""
+
+    def __init__(self):
+        self.dropout = []
+
+    def attention_fwd(self, q, k, v, scale, out=None, dropout_p=0.0, seed=0):
+        self.dropout.append((dropout_p, seed))
+        o, lse = attn_ops._composite_fwd(q.contiguous(), k.contiguous(),
+                                         v.contiguous(), scale)
+        return (o if out is None else out.copy_(o)), lse
+
+    def attention_bwd(self, q, k, v, o, lse, dout, scale, dq=None, dk=None,
+                      dv=None, dropout_p=0.0, seed=0):
+        self.dropout.append((dropout_p, seed))
+        grads = attn_ops._composite_bwd(
+            q.contiguous(), k.contiguous(), v.contiguous(), o.contiguous(),
+            lse, dout.contiguous(), scale)
+        if dq is None:
+            return grads
+        return tuple(buf.copy_(g) for buf, g in zip((dq, dk, dv), grads))
+
+
+class _RecordingTuner:
+    def __init__(self):
+        self.calls = []
+
+    def choose(self, op, candidates, *args):
+        self.calls.append((op, [c.__name__ for c in candidates], args))
+        return candidates[0](*args)
+
+
+@pytest.fixture
+def attn_kernel_path_on_cpu(monkeypatch):
+    """ops/attention.py takes its kernel path on CPU tensors: the `_ext` seam
+    reports a native extension, and the tuner is a recording stub."""
+    ext, tuner = _CompositeAttnExt(), _RecordingTuner()
+    monkeypatch.setattr(attn_ops._ext, "use_native", lambda *t: True)
+    monkeypatch.setattr(attn_ops._ext, "get_ext", lambda: ext)
+    monkeypatch.setattr(attn_ops, "default_tuner", lambda: tuner)
+    return ext, tuner
+
+
+def _attn_leaves():
+    g = torch.Generator().manual_seed(0)
+    qkv = torch.randn(1, 64, 3 * 2 * 64, generator=g).to(torch.bfloat16)
+    q, k, v = (t.contiguous().requires_grad_()
+               for t in attn_ops._packed_views(qkv, 2))
+    return qkv.requires_grad_(), q, k, v
+
+
+def test_attention_tuner_ops_candidates_and_argument_order(
+        attn_kernel_path_on_cpu):
+    """What the tuner cache file stores: the four op names, the candidates'
+    names with HIP first, and the order of the arguments given to choose."""
+    _, tuner = attn_kernel_path_on_cpu
+    qkv, q, k, v = _attn_leaves()
+    ops.causal_attention(q, k, v).sum().backward()
+    ops.fused_causal_attention(qkv, 2).sum().backward()
+    assert [(op, names) for op, names, _ in tuner.calls] == [
+        ("attn_fwd", ["attn_fwd_hip", "attn_fwd_composite"]),
+        ("attn_bwd", ["attn_bwd_hip", "attn_bwd_composite"]),
+        ("attn_fwd_packed",
+         ["attn_fwd_packed_hip", "attn_fwd_packed_composite"]),
+        ("attn_bwd_packed",
+         ["attn_bwd_packed_hip", "attn_bwd_packed_composite"]),
+    ]
+    scale = 1.0 / math.sqrt(64)
+    bhtd, bht = (1, 2, 64, 64), (1, 2, 64)
+
+    def kinds(args):
+        return [a if isinstance(a, float) else (tuple(a.shape), a.dtype)
+                for a in args]
+
+    t16, lse = (bhtd, torch.bfloat16), (bht, torch.float32)
+    fwd, bwd, fwd_p, bwd_p = (args for _, _, args in tuner.calls)
+    assert kinds(fwd) == [t16] * 3 + [scale]
+    assert all(a is b for a, b in zip(fwd[:3], (q, k, v)))
+    assert kinds(bwd) == [t16] * 4 + [lse, t16, scale]
+    assert kinds(fwd_p) == [t16] * 3 + [scale, t16]
+    assert kinds(bwd_p) == [t16] * 4 + [lse, t16, scale] + [t16] * 3
+    # packed: q, k, v and dq, dk, dv are the three slices of one buffer each
+    step = 2 * 64 * qkv.element_size()
+    for a, b, c in (fwd_p[:3], bwd_p[:3], bwd_p[7:]):
+        assert not a.is_contiguous()
+        assert b.data_ptr() - a.data_ptr() == c.data_ptr() - b.data_ptr() == step
+    assert fwd_p[0].data_ptr() == qkv.data_ptr()
+
+
+def test_attention_dropout_bypasses_tuner(attn_kernel_path_on_cpu):
+    """With dropout the HIP candidate runs directly (the composite has another
+    mask), and backward gets the forward's p and seed."""
+    ext, tuner = attn_kernel_path_on_cpu
+    qkv, q, k, v = _attn_leaves()
+    ops.causal_attention(q, k, v, dropout_p=0.25, training=True).sum().backward()
+    ops.fused_causal_attention(qkv, 2, dropout_p=0.25,
+                               training=True).sum().backward()
+    assert tuner.calls == []
+    (p0, s0), (p1, s1), (p2, s2), (p3, s3) = ext.dropout
+    assert p0 == p1 == p2 == p3 == 0.25
+    assert s0 == s1 and s2 == s3 and s0 != s2
+    # not training: no dropout, the tuner is asked
+    ops.causal_attention(q, k, v, dropout_p=0.25, training=False)
+    assert [op for op, _, _ in tuner.calls] == ["attn_fwd"]
+    assert ext.dropout[-1] == (0.0, 0)

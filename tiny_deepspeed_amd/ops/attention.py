@@ -1,8 +1,8 @@
 """Fused causal self-attention (flash-style), autograd-wrapped.
 
 The reference materializes the full (B,nh,T,T) score matrix or calls SDPA
-(``/root/reference/example/model.py:29-51``). Here: hand-written CDNA4
-MFMA kernels (csrc/attention.hip) — forward computes QK^T -> online softmax
+(its ``example/model.py``). Here: hand-written CDNA4
+MFMA kernels (csrc/kernels/attention.hip) — forward computes QK^T -> online softmax
 -> PV per K/V tile without materializing scores, saving per-row logsumexp;
 backward recomputes P from (q, k, lse) and produces dq/dk/dv in two passes.
 
@@ -123,22 +123,39 @@ def attn_bwd_packed_composite(q, k, v, o, lse, do, scale, dq, dk, dv):
     return dq, dk, dv
 
 
+def _run(op, candidates, args, dropout_p=0.0, seed=0):
+    """The one choice every kernel-path call makes. candidates[0] is the HIP
+    kernel. With dropout it runs directly, with the seed that regenerates the
+    mask in backward: the composite has a different mask, so there is nothing
+    to tune. Otherwise the tuner, if any, picks among the candidates."""
+    if dropout_p > 0.0:
+        return candidates[0](*args, dropout_p, seed)
+    tuner = default_tuner()
+    if tuner is not None:
+        return tuner.choose(op, candidates, *args)
+    return candidates[0](*args)
+
+
+def _heads_view(x, n_head):
+    """(B, T, H*D) -> (B, H, T, D) view."""
+    B, T, E = x.shape
+    return x.view(B, T, n_head, E // n_head).permute(0, 2, 1, 3)
+
+
+def _packed_views(qkv, n_head):
+    """(B, T, 3*H*D) -> the three (B, H, T, D) views of the (B,T,3,H,D)
+    layout (q, k, v of a projection output; dq, dk, dv of its gradient)."""
+    B, T, E3 = qkv.shape
+    qkv4 = qkv.view(B, T, 3, n_head, E3 // 3 // n_head)
+    return tuple(qkv4[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+
+
 class _CausalAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale, dropout_p=0.0, seed=0):
         if _ext.use_native(q) and _kernel_supported(q):
-            if dropout_p > 0.0:
-                # fused in-kernel dropout: the seed regenerates the mask in
-                # backward; no tuner (the composite has a different mask)
-                o, lse = attn_fwd_hip(q, k, v, scale, dropout_p, seed)
-            else:
-                tuner = default_tuner()
-                if tuner is not None:
-                    o, lse = tuner.choose("attn_fwd",
-                                          [attn_fwd_hip, attn_fwd_composite],
-                                          q, k, v, scale)
-                else:
-                    o, lse = attn_fwd_hip(q, k, v, scale)
+            o, lse = _run("attn_fwd", [attn_fwd_hip, attn_fwd_composite],
+                          (q, k, v, scale), dropout_p, seed)
         else:
             assert dropout_p == 0.0  # caller routes CPU dropout elsewhere
             o, lse = _composite_fwd(q, k, v, scale)
@@ -150,21 +167,12 @@ class _CausalAttentionFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
-        dropout_p, seed = ctx.dropout
+        args = (q, k, v, o, lse, do, ctx.scale)
         if _ext.use_native(q) and _kernel_supported(q):
-            if dropout_p > 0.0:
-                dq, dk, dv = attn_bwd_hip(q, k, v, o, lse, do, ctx.scale,
-                                          dropout_p, seed)
-            else:
-                tuner = default_tuner()
-                if tuner is not None:
-                    dq, dk, dv = tuner.choose(
-                        "attn_bwd", [attn_bwd_hip, attn_bwd_composite],
-                        q, k, v, o, lse, do, ctx.scale)
-                else:
-                    dq, dk, dv = attn_bwd_hip(q, k, v, o, lse, do, ctx.scale)
+            dq, dk, dv = _run("attn_bwd", [attn_bwd_hip, attn_bwd_composite],
+                              args, *ctx.dropout)
         else:
-            dq, dk, dv = _composite_bwd(q, k, v, o, lse, do, ctx.scale)
+            dq, dk, dv = _composite_bwd(*args)
         return dq, dk, dv, None, None, None
 
 
@@ -174,48 +182,25 @@ class _FusedQKVAttentionFn(torch.autograd.Function):
     The stride-aware CDNA4 kernels consume the (B,T,3,H,D) layout directly
     and write O into a (B,T,E) buffer / dQKV into a (B,T,3E) buffer — no
     transpose-copies or cat on the hot path (the reference pays 4 transposed
-    .contiguous() copies per attention plus a cat in backward,
-    /root/reference/example/model.py:67-85 via torch autograd).
+    .contiguous() copies per attention plus a cat in backward through torch
+    autograd).
     """
 
     @staticmethod
-    def _views(qkv, n_head):
-        B, T, E3 = qkv.shape
-        E = E3 // 3
-        D = E // n_head
-        qkv4 = qkv.view(B, T, 3, n_head, D)
-        q = qkv4[:, :, 0].permute(0, 2, 1, 3)  # (B,H,T,D) view
-        k = qkv4[:, :, 1].permute(0, 2, 1, 3)
-        v = qkv4[:, :, 2].permute(0, 2, 1, 3)
-        return q, k, v, B, T, E, D
-
-    @staticmethod
     def forward(ctx, qkv, n_head, scale, dropout_p=0.0, seed=0):
-        q, k, v, B, T, E, D = _FusedQKVAttentionFn._views(qkv, n_head)
-        if _ext.use_native(qkv) and _kernel_supported(q):
-            y = torch.empty(B, T, E, dtype=qkv.dtype, device=qkv.device)
-            o_view = y.view(B, T, n_head, D).permute(0, 2, 1, 3)
-            if dropout_p > 0.0:
-                # fused in-kernel dropout (seed regenerates the mask in
-                # backward); the composite candidate has a different mask,
-                # so no tuner on this path
-                o, lse = attn_fwd_packed_hip(q, k, v, scale, o_view,
-                                             dropout_p, seed)
-            else:
-                tuner = default_tuner()
-                if tuner is not None:
-                    o, lse = tuner.choose(
-                        "attn_fwd_packed",
-                        [attn_fwd_packed_hip, attn_fwd_packed_composite],
-                        q, k, v, scale, o_view)
-                else:
-                    o, lse = attn_fwd_packed_hip(q, k, v, scale, o_view)
-            ctx.native = True
+        q, k, v = _packed_views(qkv, n_head)
+        B, T, E3 = qkv.shape
+        ctx.native = _ext.use_native(qkv) and _kernel_supported(q)
+        if ctx.native:
+            y = torch.empty(B, T, E3 // 3, dtype=qkv.dtype, device=qkv.device)
+            o, lse = _run("attn_fwd_packed",
+                          [attn_fwd_packed_hip, attn_fwd_packed_composite],
+                          (q, k, v, scale, _heads_view(y, n_head)),
+                          dropout_p, seed)
         else:
             o, lse = _composite_fwd(q.contiguous(), k.contiguous(),
                                     v.contiguous(), scale)
-            y = o.permute(0, 2, 1, 3).reshape(B, T, E)
-            ctx.native = False
+            y = o.permute(0, 2, 1, 3).reshape(B, T, E3 // 3)
         ctx.save_for_backward(qkv, y, lse)
         ctx.n_head = n_head
         ctx.scale = scale
@@ -226,63 +211,40 @@ class _FusedQKVAttentionFn(torch.autograd.Function):
     def backward(ctx, dy):
         qkv, y, lse = ctx.saved_tensors
         n_head = ctx.n_head
-        q, k, v, B, T, E, D = _FusedQKVAttentionFn._views(qkv, n_head)
-        o_view = y.view(B, T, n_head, D).permute(0, 2, 1, 3)
-        do_view = dy.contiguous().view(B, T, n_head, D).permute(0, 2, 1, 3)
-        dropout_p, seed = ctx.dropout
+        q, k, v = _packed_views(qkv, n_head)
+        o_view = _heads_view(y, n_head)
+        do_view = _heads_view(dy.contiguous(), n_head)
         if ctx.native:
             dqkv = torch.empty_like(qkv)
-            dqkv4 = dqkv.view(B, T, 3, n_head, D)
-            dq = dqkv4[:, :, 0].permute(0, 2, 1, 3)
-            dk = dqkv4[:, :, 1].permute(0, 2, 1, 3)
-            dv = dqkv4[:, :, 2].permute(0, 2, 1, 3)
-            if dropout_p > 0.0:
-                attn_bwd_packed_hip(q, k, v, o_view, lse, do_view, ctx.scale,
-                                    dq, dk, dv, dropout_p, seed)
-            else:
-                tuner = default_tuner()
-                if tuner is not None:
-                    tuner.choose(
-                        "attn_bwd_packed",
-                        [attn_bwd_packed_hip, attn_bwd_packed_composite],
-                        q, k, v, o_view, lse, do_view, ctx.scale, dq, dk, dv)
-                else:
-                    attn_bwd_packed_hip(q, k, v, o_view, lse, do_view,
-                                        ctx.scale, dq, dk, dv)
+            _run("attn_bwd_packed",
+                 [attn_bwd_packed_hip, attn_bwd_packed_composite],
+                 (q, k, v, o_view, lse, do_view, ctx.scale,
+                  *_packed_views(dqkv, n_head)), *ctx.dropout)
         else:
-            dq, dk, dv = _composite_bwd(
+            grads = _composite_bwd(
                 q.contiguous(), k.contiguous(), v.contiguous(),
                 o_view.contiguous(), lse, do_view.contiguous(), ctx.scale)
             dqkv = torch.cat(
-                [g.permute(0, 2, 1, 3).reshape(B, T, E) for g in (dq, dk, dv)],
-                dim=2)
+                [g.permute(0, 2, 1, 3).reshape(y.shape) for g in grads], dim=2)
         return dqkv, None, None, None, None
 
 
 def fused_causal_attention(qkv, n_head, scale=None, dropout_p=0.0,
                            training=False):
     """qkv: (B, T, 3E) packed projection output. Returns (B, T, E)."""
-    E = qkv.shape[-1] // 3
-    D = E // n_head
     if scale is None:
-        scale = 1.0 / math.sqrt(D)
+        scale = 1.0 / math.sqrt(qkv.shape[-1] // 3 // n_head)
     p = dropout_p if training else 0.0
     if p > 0.0:
-        qkv4 = qkv.view(qkv.shape[0], qkv.shape[1], 3, n_head, D)
-        q_probe = qkv4[:, :, 0].permute(0, 2, 1, 3)
-        if _ext.use_native(qkv) and _kernel_supported(q_probe):
+        q, k, v = _packed_views(qkv, n_head)
+        if _ext.use_native(qkv) and _kernel_supported(q):
             # fused in-kernel dropout
             return _FusedQKVAttentionFn.apply(qkv, n_head, scale, p,
                                               _draw_seed())
         # CPU/off-design shapes: unpack to the composite autograd path
-        B, T, _ = qkv.shape
-        q, k, v = qkv.split(E, dim=2)
-        q = q.view(B, T, n_head, D).transpose(1, 2)
-        k = k.view(B, T, n_head, D).transpose(1, 2)
-        v = v.view(B, T, n_head, D).transpose(1, 2)
         y = causal_attention(q.contiguous(), k.contiguous(), v.contiguous(),
                              scale, p, training)
-        return y.transpose(1, 2).reshape(B, T, E)
+        return y.transpose(1, 2).reshape(y.shape[0], y.shape[2], -1)
     return _FusedQKVAttentionFn.apply(qkv, n_head, scale)
 
 
