@@ -7,59 +7,13 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "kernels/launchers.h"
 #include "kernels/optim_desc.h"
 
 #include <array>
+#include <climits>
 #include <cstring>
 #include <vector>
-
-// ---- extern "C" launcher prototypes (csrc/kernels/*.hip) ------------------
-extern "C" {
-hipError_t tdsa_ln_fwd(const void*, const void*, void*, const void*,
-                       const void*, void*, float*, float*, int, int, float,
-                       int, hipStream_t);
-int tdsa_ln_bwd_dx_stripes(int M, int N, int is_bf16);
-void tdsa_ln_rowwave_info(int, int, int, int*, int*, int*, int*);
-hipError_t tdsa_ln_bwd_dx(const void*, const void*, const void*, const void*,
-                          const float*, const float*, void*, float*, float*,
-                          int, int, int, hipStream_t);
-hipError_t tdsa_ln_bwd_dwdb(const float*, const float*, void*, void*, int, int,
-                            int, hipStream_t);
-hipError_t tdsa_gelu_fwd(const void*, void*, long long, int, hipStream_t);
-hipError_t tdsa_gelu_bwd(const void*, const void*, void*, long long, int,
-                         hipStream_t);
-hipError_t tdsa_column_sum(const void*, float*, void*, int, int, int,
-                           hipStream_t);
-hipError_t tdsa_embedding_fwd(const void*, const long long*, void*, long long,
-                              int, int, hipStream_t);
-hipError_t tdsa_embedding_bwd(const void*, const long long*, const long long*,
-                              float*, float*, long long, int, long long, int,
-                              hipStream_t);
-hipError_t tdsa_ce_fwd(const void*, const long long*, float*, float*, int*,
-                       long long, int, long long, int, hipStream_t);
-hipError_t tdsa_ce_bwd(const void*, const long long*, const float*, void*,
-                       long long, int, float, long long, int, hipStream_t);
-hipError_t tdsa_adamw_multi(const void*, int, int, int, float, float, float,
-                            float, float, long long, hipStream_t);
-hipError_t tdsa_sgd_multi(const void*, int, int, float, float, float, float,
-                          int, int, hipStream_t);
-hipError_t tdsa_attn_fwd(const void*, const void*, const void*, void*, float*,
-                         long long, long long, int, float, const long long*,
-                         const long long*, float, unsigned long long,
-                         hipStream_t);
-hipError_t tdsa_attn_bwd(const void*, const void*, const void*, const void*,
-                         const float*, const void*, void*, void*, void*, float*,
-                         long long, long long, int, float, const long long*,
-                         const long long*, const long long*, float,
-                         unsigned long long, hipStream_t);
-int tdsa_gemm_tn_splits(long long M, int N, int K);
-hipError_t tdsa_gemm_tn(const void*, const void*, float*, long long, int, int,
-                        hipStream_t);
-hipError_t tdsa_dbg_mfma(const void*, const void*, float*, int, hipStream_t);
-hipError_t tdsa_dbg_mfma32(const void*, const void*, float*, hipStream_t);
-hipError_t tdsa_dbg_stage(const void*, void*, int, hipStream_t);
-hipError_t tdsa_dbg_tr16(const void*, float*, hipStream_t);
-}
 
 namespace {
 
@@ -78,17 +32,67 @@ hipStream_t cur_stream() {
   return (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
 }
 
-#define CHECK_IN(t)                                                     \
-  TORCH_CHECK((t).is_cuda(), #t " must be on GPU");                     \
-  TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
+// ---- argument checks of the non-attention, non-optimizer bindings ---------
+// One argument of a call; an absent optional one is skipped. Every argument
+// must be on the first one's GPU. dtype: the one it must have; none means
+// the first argument's, which itself must be float32 or bfloat16. numel: its
+// element count (kAny: not checked). strided: the binding makes its own
+// contiguous copy, so any layout is accepted.
+constexpr int64_t kAny = -1;
+struct Arg {
+  const char* name;
+  c10::optional<at::Tensor> t;
+  c10::optional<at::ScalarType> dtype;
+  int64_t numel;
+  bool strided = false;
+};
+
+// Checks all of `args` in one pass, before anything is allocated or
+// launched, and returns the first argument's dtype flag.
+int check_call(const char* op, std::initializer_list<Arg> args) {
+  const at::Tensor& first = *args.begin()->t;
+  for (const Arg& a : args) {
+    if (!a.t.has_value()) continue;
+    const at::Tensor& t = *a.t;
+    TORCH_CHECK(t.is_cuda(), op, ": ", a.name, " must be on GPU");
+    TORCH_CHECK(t.device() == first.device(), op, ": ", a.name, " is on ",
+                t.device(), ", ", args.begin()->name, " on ", first.device());
+    TORCH_CHECK(a.strided || t.is_contiguous(), op, ": ", a.name,
+                " must be contiguous");
+    const at::ScalarType want = a.dtype.value_or(first.scalar_type());
+    TORCH_CHECK(t.scalar_type() == want, op, ": ", a.name, " must be ", want,
+                ", got ", t.scalar_type());
+    TORCH_CHECK(a.numel == kAny || t.numel() == a.numel, op, ": ", a.name,
+                " has ", t.numel(), " elements, expected ", a.numel);
+  }
+  return dtype_flag(first);
+}
+
+// A row count or width as the `int` a launcher takes.
+int as_int(const char* op, const char* name, int64_t v) {
+  TORCH_CHECK(v >= 0 && v <= INT_MAX, op, ": ", name, " = ", v,
+              " does not fit the launcher's int");
+  return (int)v;
+}
+
+// Row width N (> 0) and row count M of a LayerNorm input.
+void ln_rows(const char* op, const at::Tensor& x, int* M, int* N) {
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0, op,
+              ": x must have a non-empty last dim, got ", x.sizes());
+  *N = as_int(op, "N", x.size(-1));
+  *M = as_int(op, "M", x.numel() / *N);
+}
 
 // ---- layernorm ------------------------------------------------------------
 std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, at::Tensor b,
                                       double eps,
                                       c10::optional<at::Tensor> res) {
-  CHECK_IN(x); CHECK_IN(w); CHECK_IN(b);
-  const int N = x.size(-1);
-  const long long M = x.numel() / N;
+  const char* op = "layernorm_fwd";
+  int M, N;
+  ln_rows(op, x, &M, &N);
+  const int flag = check_call(op, {{"x", x, {}, kAny}, {"w", w, {}, N},
+                                   {"b", b, {}, N},
+                                   {"res", res, {}, x.numel()}});
   auto y = at::empty_like(x);
   auto f32 = x.options().dtype(at::kFloat);
   auto mean = at::empty({M}, f32);
@@ -97,16 +101,15 @@ std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, at::Tensor b,
   void* res_p = nullptr;
   void* h_p = nullptr;
   if (res.has_value()) {
-    CHECK_IN((*res));
     h = at::empty_like(x);
     res_p = res->data_ptr();
     h_p = h.data_ptr();
   }
   check_hip(tdsa_ln_fwd(x.data_ptr(), res_p, h_p, w.data_ptr(), b.data_ptr(),
                         y.data_ptr(), mean.data_ptr<float>(),
-                        rstd.data_ptr<float>(), (int)M, N, (float)eps,
-                        dtype_flag(x), cur_stream()),
-            "layernorm_fwd");
+                        rstd.data_ptr<float>(), M, N, (float)eps, flag,
+                        cur_stream()),
+            op);
   // mean/rstd viewed to the row shape of x
   auto row_sizes = x.sizes().vec();
   row_sizes.pop_back();
@@ -119,10 +122,16 @@ std::vector<at::Tensor> layernorm_bwd_dx(at::Tensor dy, at::Tensor x,
                                          at::Tensor w, at::Tensor mean,
                                          at::Tensor rstd,
                                          c10::optional<at::Tensor> dh) {
-  CHECK_IN(dy); CHECK_IN(x); CHECK_IN(w);
-  const int N = x.size(-1);
-  const long long M = x.numel() / N;
-  const int G = tdsa_ln_bwd_dx_stripes((int)M, N, dtype_flag(x));
+  const char* op = "layernorm_bwd_dx";
+  int M, N;
+  ln_rows(op, x, &M, &N);
+  const int flag = check_call(op, {{"x", x, {}, kAny},
+                                   {"dy", dy, {}, x.numel()},
+                                   {"w", w, {}, N},
+                                   {"mean", mean, at::kFloat, M, true},
+                                   {"rstd", rstd, at::kFloat, M, true},
+                                   {"dh", dh, {}, x.numel(), true}});
+  const int G = tdsa_ln_bwd_dx_stripes(M, N, flag);
   auto dx = at::empty_like(x);
   auto f32 = x.options().dtype(at::kFloat);
   auto pdw = at::empty({G, N}, f32);
@@ -138,9 +147,8 @@ std::vector<at::Tensor> layernorm_bwd_dx(at::Tensor dy, at::Tensor x,
   check_hip(tdsa_ln_bwd_dx(dy.data_ptr(), dh_p, x.data_ptr(), w.data_ptr(),
                            meanc.data_ptr<float>(), rstdc.data_ptr<float>(),
                            dx.data_ptr(), pdw.data_ptr<float>(),
-                           pdb.data_ptr<float>(), (int)M, N, dtype_flag(x),
-                           cur_stream()),
-            "layernorm_bwd_dx");
+                           pdb.data_ptr<float>(), M, N, flag, cur_stream()),
+            op);
   return {dx, pdw, pdb};
 }
 
@@ -148,18 +156,21 @@ std::vector<at::Tensor> layernorm_bwd_dx(at::Tensor dy, at::Tensor x,
 // the fp32 sums); fp32 when absent.
 std::vector<at::Tensor> layernorm_bwd_dwdb(
     at::Tensor pdw, at::Tensor pdb, c10::optional<at::ScalarType> dtype) {
-  CHECK_IN(pdw); CHECK_IN(pdb);
+  const char* op = "layernorm_bwd_dwdb";
+  check_call(op, {{"pdw", pdw, at::kFloat, kAny},
+                  {"pdb", pdb, at::kFloat, pdw.numel()}});
+  TORCH_CHECK(pdw.dim() == 2, op, ": pdw must be 2-D, got ", pdw.sizes());
   const at::ScalarType out = dtype.value_or(at::kFloat);
   TORCH_CHECK(out == at::kFloat || out == at::kBFloat16,
               "layernorm_bwd_dwdb: dtype must be float32 or bfloat16");
-  const int G = pdw.size(0);
-  const int N = pdw.size(1);
+  const int G = as_int(op, "G", pdw.size(0));
+  const int N = as_int(op, "N", pdw.size(1));
   auto dw = at::empty({N}, pdw.options().dtype(out));
   auto db = at::empty({N}, pdb.options().dtype(out));
   check_hip(tdsa_ln_bwd_dwdb(pdw.data_ptr<float>(), pdb.data_ptr<float>(),
                              dw.data_ptr(), db.data_ptr(), G, N,
                              out == at::kBFloat16, cur_stream()),
-            "layernorm_bwd_dwdb");
+            op);
   return {dw, db};
 }
 
@@ -176,56 +187,63 @@ std::vector<int64_t> layernorm_rowwave_geometry(int64_t M, int64_t N,
 
 // ---- elementwise ----------------------------------------------------------
 at::Tensor gelu_fwd(at::Tensor x) {
-  CHECK_IN(x);
+  const int flag = check_call("gelu_fwd", {{"x", x, {}, kAny}});
   auto y = at::empty_like(x);
-  check_hip(tdsa_gelu_fwd(x.data_ptr(), y.data_ptr(), x.numel(), dtype_flag(x),
+  check_hip(tdsa_gelu_fwd(x.data_ptr(), y.data_ptr(), x.numel(), flag,
                           cur_stream()),
             "gelu_fwd");
   return y;
 }
 
 at::Tensor gelu_bwd(at::Tensor dy, at::Tensor x) {
-  CHECK_IN(dy); CHECK_IN(x);
+  const int flag = check_call("gelu_bwd", {{"x", x, {}, kAny},
+                                           {"dy", dy, {}, x.numel()}});
   auto dx = at::empty_like(x);
   check_hip(tdsa_gelu_bwd(dy.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(),
-                          dtype_flag(x), cur_stream()),
+                          flag, cur_stream()),
             "gelu_bwd");
   return dx;
 }
 
 at::Tensor column_sum(at::Tensor dy) {
-  CHECK_IN(dy);
+  const char* op = "column_sum";
+  const int flag = check_call(op, {{"dy", dy, {}, kAny}});
   TORCH_CHECK(dy.dim() == 2, "column_sum expects 2-D input");
-  const int M = dy.size(0);
-  const int N = dy.size(1);
+  const int M = as_int(op, "M", dy.size(0));
+  const int N = as_int(op, "N", dy.size(1));
   auto out32 = at::zeros({N}, dy.options().dtype(at::kFloat));
   auto out = at::empty({N}, dy.options());
   check_hip(tdsa_column_sum(dy.data_ptr(), out32.data_ptr<float>(),
-                            out.data_ptr(), M, N, dtype_flag(dy), cur_stream()),
-            "column_sum");
+                            out.data_ptr(), M, N, flag, cur_stream()),
+            op);
   return out;
 }
 
 // ---- embedding ------------------------------------------------------------
 at::Tensor embedding_fwd(at::Tensor weight, at::Tensor idx) {
-  CHECK_IN(weight); CHECK_IN(idx);
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
+  const char* op = "embedding_fwd";
+  const int flag = check_call(op, {{"weight", weight, {}, kAny},
+                                   {"idx", idx, at::kLong, kAny}});
+  TORCH_CHECK(weight.dim() == 2, op, ": weight must be 2-D, got ",
+              weight.sizes());
   const long long R = idx.numel();
-  const int D = weight.size(1);
+  const int D = as_int(op, "D", weight.size(1));
   auto out = at::empty({R, (long long)D}, weight.options());
   check_hip(tdsa_embedding_fwd(weight.data_ptr(), (const long long*)idx.data_ptr<int64_t>(),
-                               out.data_ptr(), R, D, dtype_flag(weight),
-                               cur_stream()),
-            "embedding_fwd");
+                               out.data_ptr(), R, D, flag, cur_stream()),
+            op);
   return out;
 }
 
 at::Tensor embedding_bwd(at::Tensor dy, at::Tensor idx, int64_t num_embeddings,
                          int64_t padding_idx) {
-  CHECK_IN(dy); CHECK_IN(idx);
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
+  const char* op = "embedding_bwd";
+  const int flag = check_call(op, {{"dy", dy, {}, kAny},
+                                   {"idx", idx, at::kLong, kAny}});
   const long long R = idx.numel();
-  const int D = dy.size(-1);
+  TORCH_CHECK(dy.dim() >= 1 && dy.numel() == R * dy.size(-1), op,
+              ": dy must have idx.numel() = ", R, " rows, got ", dy.sizes());
+  const int D = as_int(op, "D", dy.size(-1));
   auto dw32 = at::zeros({num_embeddings, (long long)D},
                         dy.options().dtype(at::kFloat));
   // stable sort: equal indices keep their dy-row order, so every table row
@@ -239,20 +257,20 @@ at::Tensor embedding_bwd(at::Tensor dy, at::Tensor idx, int64_t num_embeddings,
   check_hip(tdsa_embedding_bwd(dy.data_ptr(), (const long long*)sidx.data_ptr<int64_t>(),
                                (const long long*)perm.data_ptr<int64_t>(),
                                dw32.data_ptr<float>(), part.data_ptr<float>(),
-                               R, D, padding_idx, dtype_flag(dy),
-                               cur_stream()),
-            "embedding_bwd");
+                               R, D, padding_idx, flag, cur_stream()),
+            op);
   return dw32;
 }
 
 // ---- cross entropy --------------------------------------------------------
 std::vector<at::Tensor> cross_entropy_fwd(at::Tensor logits, at::Tensor targets,
                                           int64_t ignore_index) {
-  CHECK_IN(logits); CHECK_IN(targets);
-  TORCH_CHECK(logits.dim() == 2, "logits must be 2-D");
-  TORCH_CHECK(targets.scalar_type() == at::kLong, "targets must be int64");
+  const char* op = "cross_entropy_fwd";
+  TORCH_CHECK(logits.dim() == 2, op, ": logits must be 2-D");
   const long long R = logits.size(0);
-  const int V = logits.size(1);
+  const int V = as_int(op, "V", logits.size(1));
+  const int flag = check_call(op, {{"logits", logits, {}, kAny},
+                                   {"targets", targets, at::kLong, R}});
   auto f32 = logits.options().dtype(at::kFloat);
   auto lse = at::empty({R}, f32);
   // per-row losses, summed below in torch's fixed reduction order
@@ -260,9 +278,9 @@ std::vector<at::Tensor> cross_entropy_fwd(at::Tensor logits, at::Tensor targets,
   auto n_valid32 = at::zeros({}, logits.options().dtype(at::kInt));
   check_hip(tdsa_ce_fwd(logits.data_ptr(), (const long long*)targets.data_ptr<int64_t>(),
                         lse.data_ptr<float>(), row_loss.data_ptr<float>(),
-                        n_valid32.data_ptr<int>(), R, V, ignore_index,
-                        dtype_flag(logits), cur_stream()),
-            "cross_entropy_fwd");
+                        n_valid32.data_ptr<int>(), R, V, ignore_index, flag,
+                        cur_stream()),
+            op);
   return {row_loss.sum(), lse, n_valid32.to(at::kLong)};
 }
 
@@ -270,24 +288,24 @@ at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor targets,
                              at::Tensor lse, double dloss, int64_t n_valid,
                              int64_t ignore_index,
                              c10::optional<at::Tensor> out) {
-  CHECK_IN(logits); CHECK_IN(targets); CHECK_IN(lse);
+  const char* op = "cross_entropy_bwd";
+  TORCH_CHECK(logits.dim() == 2, op, ": logits must be 2-D");
   const long long R = logits.size(0);
-  const int V = logits.size(1);
-  at::Tensor dlogits;
-  if (out.has_value()) {  // e.g. a row-slice of the fused-CE dlogits buffer
-    dlogits = *out;
-    CHECK_IN(dlogits);
-    TORCH_CHECK(dlogits.sizes() == logits.sizes()
-                && dlogits.scalar_type() == logits.scalar_type(),
-                "cross_entropy_bwd: out must match logits");
-  } else {
-    dlogits = at::empty_like(logits);
-  }
+  const int V = as_int(op, "V", logits.size(1));
+  // out: e.g. a row-slice of the fused-CE dlogits buffer
+  at::Tensor dlogits = out.has_value() ? *out : at::empty_like(logits);
+  const int flag = check_call(op, {{"logits", logits, {}, kAny},
+                                   {"targets", targets, at::kLong, R},
+                                   {"lse", lse, at::kFloat, R},
+                                   {"out", dlogits, {}, kAny}});
+  TORCH_CHECK(dlogits.sizes() == logits.sizes(), op,
+              ": out must have logits' sizes ", logits.sizes(), ", got ",
+              dlogits.sizes());
   const float scale = (float)(dloss / (double)std::max<int64_t>(n_valid, 1));
   check_hip(tdsa_ce_bwd(logits.data_ptr(), (const long long*)targets.data_ptr<int64_t>(),
                         lse.data_ptr<float>(), dlogits.data_ptr(), R, V, scale,
-                        ignore_index, dtype_flag(logits), cur_stream()),
-            "cross_entropy_bwd");
+                        ignore_index, flag, cur_stream()),
+            op);
   return dlogits;
 }
 
@@ -414,14 +432,14 @@ void sgd_step_multi(std::vector<at::Tensor> params,
 
 // ---- TN GEMM (linear dW autotuner candidate) ------------------------------
 at::Tensor gemm_tn(at::Tensor dy2, at::Tensor x2) {
-  CHECK_IN(dy2); CHECK_IN(x2);
+  const char* op = "gemm_tn";
+  check_call(op, {{"dy2", dy2, at::kBFloat16, kAny},
+                  {"x2", x2, at::kBFloat16, kAny}});
   TORCH_CHECK(dy2.dim() == 2 && x2.dim() == 2, "gemm_tn expects 2-D inputs");
-  TORCH_CHECK(dy2.scalar_type() == at::kBFloat16
-              && x2.scalar_type() == at::kBFloat16, "gemm_tn is bf16-only");
-  TORCH_CHECK(dy2.size(0) == x2.size(0), "reduction dims differ");
+  TORCH_CHECK(dy2.size(0) == x2.size(0), "gemm_tn: reduction dims differ");
   const long long M = dy2.size(0);
-  const int N = dy2.size(1);
-  const int K = x2.size(1);
+  const int N = as_int(op, "N", dy2.size(1));
+  const int K = as_int(op, "K", x2.size(1));
   const int splits = tdsa_gemm_tn_splits(M, N, K);
   TORCH_CHECK(splits > 0, "gemm_tn: unsupported shape (need M%64==0, "
               "N%128==0, K%128==0), got ", M, "x", N, "/", K);
@@ -511,7 +529,8 @@ std::vector<at::Tensor> attention_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
 
 // ---- debug probes ---------------------------------------------------------
 at::Tensor dbg_mfma(at::Tensor A, at::Tensor B, int64_t variant) {
-  CHECK_IN(A); CHECK_IN(B);
+  check_call("dbg_mfma", {{"A", A, at::kBFloat16, 16 * 32},
+                          {"B", B, at::kBFloat16, 32 * 16}});
   auto D = at::zeros({16, 16}, A.options().dtype(at::kFloat));
   check_hip(tdsa_dbg_mfma(A.data_ptr(), B.data_ptr(), D.data_ptr<float>(),
                           (int)variant, cur_stream()),
@@ -520,7 +539,8 @@ at::Tensor dbg_mfma(at::Tensor A, at::Tensor B, int64_t variant) {
 }
 
 at::Tensor dbg_mfma32(at::Tensor A, at::Tensor B) {
-  CHECK_IN(A); CHECK_IN(B);
+  check_call("dbg_mfma32", {{"A", A, at::kBFloat16, 32 * 16},
+                            {"B", B, at::kBFloat16, 16 * 32}});
   auto D = at::zeros({32, 32}, A.options().dtype(at::kFloat));
   check_hip(tdsa_dbg_mfma32(A.data_ptr(), B.data_ptr(), D.data_ptr<float>(),
                             cur_stream()),
@@ -529,7 +549,7 @@ at::Tensor dbg_mfma32(at::Tensor A, at::Tensor B) {
 }
 
 at::Tensor dbg_stage(at::Tensor in, int64_t transposed) {
-  CHECK_IN(in);
+  check_call("dbg_stage", {{"in", in, at::kBFloat16, 64 * 64}});
   auto out = at::zeros_like(in);
   check_hip(tdsa_dbg_stage(in.data_ptr(), out.data_ptr(), (int)transposed,
                            cur_stream()),
@@ -538,7 +558,7 @@ at::Tensor dbg_stage(at::Tensor in, int64_t transposed) {
 }
 
 at::Tensor dbg_tr16(at::Tensor in) {
-  CHECK_IN(in);
+  check_call("dbg_tr16", {{"in", in, at::kBFloat16, 64 * 64}});
   auto out = at::zeros({2, 4, 2, 4, 64}, in.options().dtype(at::kFloat));
   check_hip(tdsa_dbg_tr16(in.data_ptr(), out.data_ptr<float>(), cur_stream()),
             "dbg_tr16");

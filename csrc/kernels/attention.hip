@@ -41,6 +41,7 @@
 // Contract: bf16, head_dim 64, T % 64 == 0 (the Python op falls back to a
 // composite rocBLAS path otherwise, ops/attention.py).
 #include "common.h"
+#include "launchers.h"
 #include "mfma.h"
 
 #include <type_traits>

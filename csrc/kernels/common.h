@@ -20,7 +20,6 @@ typedef __hip_bfloat16 bf16;
 // ---- vector types ---------------------------------------------------------
 typedef __attribute__((ext_vector_type(4))) short short4v;
 typedef __attribute__((ext_vector_type(8))) short short8v;
-typedef __attribute__((ext_vector_type(4))) float float4v;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
@@ -41,6 +40,39 @@ DEV_INLINE float bf_elem(V v, int i) {
 DEV_INLINE short bf_pack(float x) {
   union { short s; bf16 b; } u; u.b = f2bf(x); return u.s;
 }
+
+// ---- Vec<T, W>: W elements of T moved as one access, read/written as fp32 ---
+// The default width is 16 bytes per lane (4 float, 8 bf16); bf16 also comes
+// 4 wide (8 bytes, next to an fp32 vector of 4), and W = 1 is the plain
+// element, so a scalar path instantiates the same template as a vector one.
+template <typename T> constexpr int kVecWidth = 16 / sizeof(T);
+template <typename T, int W_ = kVecWidth<T>> struct Vec;
+template <> struct Vec<float, 4> {
+  static constexpr int W = 4;
+  typedef f32x4 V;
+  static DEV_INLINE V load(const float* p) { return *reinterpret_cast<const V*>(p); }
+  static DEV_INLINE void store(float* p, V v) { *reinterpret_cast<V*>(p) = v; }
+  static DEV_INLINE float get(V v, int i) { return v[i]; }
+  static DEV_INLINE void set(V& v, int i, float x) { v[i] = x; }
+};
+template <int W_> struct BfVec {  // bf16 x 4 or 8, carried as shorts
+  static constexpr int W = W_;
+  typedef __attribute__((ext_vector_type(W_))) short V;
+  static DEV_INLINE V load(const bf16* p) { return *reinterpret_cast<const V*>(p); }
+  static DEV_INLINE void store(bf16* p, V v) { *reinterpret_cast<V*>(p) = v; }
+  static DEV_INLINE float get(V v, int i) { return bf_elem(v, i); }
+  static DEV_INLINE void set(V& v, int i, float x) { v[i] = bf_pack(x); }
+};
+template <> struct Vec<bf16, 8> : BfVec<8> {};
+template <> struct Vec<bf16, 4> : BfVec<4> {};
+template <typename T> struct Vec<T, 1> {
+  static constexpr int W = 1;
+  typedef T V;
+  static DEV_INLINE V load(const T* p) { return *p; }
+  static DEV_INLINE void store(T* p, V v) { *p = v; }
+  static DEV_INLINE float get(V v, int) { return (float)v; }
+  static DEV_INLINE void set(V& v, int, float x) { v = (T)x; }
+};
 
 // ---- wave reductions ------------------------------------------------------
 DEV_INLINE float wave_sum(float v) {
@@ -119,6 +151,17 @@ DEV_INLINE float block_max(float v, float* scratch) {
 inline long long env_int(const char* name, long long dflt) {
   const char* v = getenv(name);
   return v ? atoll(v) : dflt;
+}
+
+// A launcher's is_bf16 flag becomes a type: calls f with TypeTag<bf16> or
+// TypeTag<float> and returns what f returns.
+//   dispatch_dtype(is_bf16, [&](auto tag) {
+//     using T = typename decltype(tag)::type; ... kernel<T> ... });
+template <typename T> struct TypeTag { typedef T type; };
+template <typename F>
+inline auto dispatch_dtype(int is_bf16, F f) {
+  if (is_bf16) return f(TypeTag<bf16>{});
+  return f(TypeTag<float>{});
 }
 
 DEV_INLINE int global_tid() { return blockIdx.x * blockDim.x + threadIdx.x; }

@@ -6,6 +6,7 @@
 // rule as flash attention) plus the picked-logit lookup; backward is one
 // pass writing (softmax - onehot) * scale. fp32 accumulation throughout.
 #include "common.h"
+#include "launchers.h"
 
 namespace tdsa {
 
@@ -21,11 +22,15 @@ DEV_INLINE void lse_scales(float& m, float m2, float& a, float& b) {
   m = mn;
 }
 
-// merge two (m, s) logsumexp states
+// merge two (m, s) logsumexp states: the incoming product is rounded, then
+// one fma adds the scaled own sum. Written out because the compiler, left to
+// contract s*a + s2*b itself, picks the product to round by the code around
+// it; this is the form it had picked in all but one merge step (see
+// lse_wave_merge).
 DEV_INLINE void lse_merge(float& m, float& s, float m2, float s2) {
   float a, b;
   lse_scales(m, m2, a, b);
-  s = s * a + s2 * b;
+  s = fmaf(s, a, s2 * b);
 }
 
 // The same merge for the per-chunk loop, with both products rounded before
@@ -39,33 +44,36 @@ DEV_INLINE void lse_merge_chunk(float& m, float& s, float m2, float s2) {
   s = s * a + s2 * b;
 }
 
-template <typename T, int W>
-struct RowVec;
-template <> struct RowVec<float, 4> {
-  typedef float4v V;
-  static DEV_INLINE V load(const float* p) { return *reinterpret_cast<const V*>(p); }
-  static DEV_INLINE float get(V v, int i) { return v[i]; }
-  static DEV_INLINE void set(V& v, int i, float x) { v[i] = x; }
-  static DEV_INLINE void store(float* p, V v) { *reinterpret_cast<V*>(p) = v; }
-};
-template <> struct RowVec<bf16, 8> {
-  typedef short8v V;
-  static DEV_INLINE V load(const bf16* p) { return load8(p); }
-  static DEV_INLINE float get(V v, int i) { return bf_elem(v, i); }
-  static DEV_INLINE void set(V& v, int i, float x) { v[i] = bf_pack(x); }
-  static DEV_INLINE void store(bf16* p, V v) { store8(p, v); }
-};
+// Merges the (m, s) states of a wave's 64 lanes; every lane ends with the
+// result. Used on the threads of a wave and again on the per-wave results.
+// ROUND_LAST: the last step rounds both products (lse_merge_chunk's form).
+// That is how the step was compiled at the thread level before the forms
+// were written out, and lse keeps those bits.
+template <bool ROUND_LAST>
+DEV_INLINE void lse_wave_merge(float& m, float& s) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float m2 = __shfl_xor(m, off, WAVE);
+    const float s2 = __shfl_xor(s, off, WAVE);
+    if (ROUND_LAST && off == 1)
+      lse_merge_chunk(m, s, m2, s2);
+    else
+      lse_merge(m, s, m2, s2);
+  }
+}
 
 // One workgroup per row (grid-strided). Writes lse[row] and the row's loss
 // row_loss[row] (fp32, 0 for ignored rows; the caller sums them in a fixed
 // order) and atomically counts n_valid (int32, order-independent).
+// Precondition, enforced by the launcher: V % W == 0, so a row is whole
+// vectors and every row base is 16-byte aligned.
 template <typename T, int W>
 __global__ void ce_fwd_kernel(const T* __restrict__ logits,
                               const long long* __restrict__ targets,
                               float* __restrict__ lse, float* __restrict__ row_loss,
                               int* __restrict__ n_valid, long long R, int V,
                               long long ignore_index) {
-  using RV = RowVec<T, W>;
+  using RV = Vec<T, W>;
   __shared__ float sm[1024 / WAVE];
   __shared__ float ssum[1024 / WAVE];
   const int tid = threadIdx.x;
@@ -99,34 +107,13 @@ __global__ void ce_fwd_kernel(const T* __restrict__ logits,
                                      * (RV::get(v, k) - sub));
       lse_merge_chunk(m, s, cm, cs);
     }
-    const int rem0 = (V / W) * W;
-    for (int j = rem0 + tid; j < V; j += blockDim.x) {
-      float f = (float)lr[j];
-      if (f > m) {
-        s = s * __expf(m - f) + 1.0f;
-        m = f;
-      } else {
-        s += __expf(f - m);
-      }
-    }
-    // wave merge
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      float m2 = __shfl_xor(m, off, WAVE);
-      float s2 = __shfl_xor(s, off, WAVE);
-      lse_merge(m, s, m2, s2);
-    }
+    lse_wave_merge<true>(m, s);
     if (lane == 0) { sm[wid] = m; ssum[wid] = s; }
     __syncthreads();
     if (wid == 0) {
       float mm = (lane < nw) ? sm[lane] : -INFINITY;
       float ss2 = (lane < nw) ? ssum[lane] : 0.f;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        float m2 = __shfl_xor(mm, off, WAVE);
-        float s2 = __shfl_xor(ss2, off, WAVE);
-        lse_merge(mm, ss2, m2, s2);
-      }
+      lse_wave_merge<false>(mm, ss2);
       if (lane == 0) {
         float l = mm + __logf(ss2);
         lse[row] = l;
@@ -145,13 +132,14 @@ __global__ void ce_fwd_kernel(const T* __restrict__ logits,
 }
 
 // dlogits = valid ? (exp(logit - lse) - onehot) * scale : 0
+// Precondition, enforced by the launcher: V % W == 0 (see ce_fwd_kernel).
 template <typename T, int W>
 __global__ void ce_bwd_kernel(const T* __restrict__ logits,
                               const long long* __restrict__ targets,
                               const float* __restrict__ lse, T* __restrict__ dlogits,
                               long long R, int V, float scale,
                               long long ignore_index) {
-  using RV = RowVec<T, W>;
+  using RV = Vec<T, W>;
   for (long long row = blockIdx.x; row < R; row += gridDim.x) {
     const T* lr = logits + row * V;
     T* dr = dlogits + row * V;
@@ -173,18 +161,21 @@ __global__ void ce_bwd_kernel(const T* __restrict__ logits,
       }
       RV::store(dr + i, out);
     }
-    // tail
-    int rem0 = (V / W) * W;
-    for (int j = rem0 + threadIdx.x; j < V; j += blockDim.x) {
-      float g = 0.f;
-      if (valid) {
-        g = __expf((float)lr[j] - l);
-        if ((long long)j == t) g -= 1.0f;
-        g *= scale;
-      }
-      dr[j] = (T)g;
-    }
   }
+}
+
+// What both launchers share. The kernels take whole 16-byte vectors only
+// and row bases logits + row * V must stay 16-byte aligned, so V % W != 0 is
+// refused (as the layernorm launchers do; the python op routes such shapes
+// to the composite). Otherwise calls launch(type tag, grid, block) with one
+// workgroup per row up to the TDSA_CE_GRID cap.
+template <typename Launch>
+static hipError_t ce_launch(long long R, int V, int is_bf16, Launch launch) {
+  if (V % (is_bf16 ? Vec<bf16>::W : Vec<float>::W)) return hipErrorInvalidValue;
+  const long long cap = env_int("TDSA_CE_GRID", 32768);
+  const int grid = (int)((R < cap) ? R : cap);
+  dispatch_dtype(is_bf16, [&](auto tag) { launch(tag, dim3(grid), dim3(256)); });
+  return hipGetLastError();
 }
 
 }  // namespace tdsa
@@ -196,41 +187,24 @@ extern "C" {
 hipError_t tdsa_ce_fwd(const void* logits, const long long* targets, float* lse,
                        float* row_loss, int* n_valid, long long R, int V,
                        long long ignore_index, int is_bf16, hipStream_t stream) {
-  const int block = 256;
-  // Row bases logits+row*V must stay 16B-aligned for the vector loads:
-  // reject V % W != 0 (mirrors the layernorm launcher guard; the python op
-  // routes such shapes to the composite path instead).
-  if (V % (is_bf16 ? 8 : 4)) return hipErrorInvalidValue;
-  const long long cap = env_int("TDSA_CE_GRID", 32768);
-  const int grid = (int)((R < cap) ? R : cap);
-  if (is_bf16)
-    hipLaunchKernelGGL((ce_fwd_kernel<bf16, 8>), dim3(grid), dim3(block), 0,
-                       stream, (const bf16*)logits, targets, lse, row_loss,
-                       n_valid, R, V, ignore_index);
-  else
-    hipLaunchKernelGGL((ce_fwd_kernel<float, 4>), dim3(grid), dim3(block), 0,
-                       stream, (const float*)logits, targets, lse, row_loss,
-                       n_valid, R, V, ignore_index);
-  return hipGetLastError();
+  return ce_launch(R, V, is_bf16, [&](auto tag, dim3 grid, dim3 block) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((ce_fwd_kernel<T, Vec<T>::W>), grid, block, 0, stream,
+                       (const T*)logits, targets, lse, row_loss, n_valid, R, V,
+                       ignore_index);
+  });
 }
 
 hipError_t tdsa_ce_bwd(const void* logits, const long long* targets,
                        const float* lse, void* dlogits, long long R, int V,
                        float scale, long long ignore_index, int is_bf16,
                        hipStream_t stream) {
-  const int block = 256;
-  if (V % (is_bf16 ? 8 : 4)) return hipErrorInvalidValue;  // see tdsa_ce_fwd
-  const long long cap = env_int("TDSA_CE_GRID", 32768);
-  const int grid = (int)((R < cap) ? R : cap);
-  if (is_bf16)
-    hipLaunchKernelGGL((ce_bwd_kernel<bf16, 8>), dim3(grid), dim3(block), 0,
-                       stream, (const bf16*)logits, targets, lse, (bf16*)dlogits,
-                       R, V, scale, ignore_index);
-  else
-    hipLaunchKernelGGL((ce_bwd_kernel<float, 4>), dim3(grid), dim3(block), 0,
-                       stream, (const float*)logits, targets, lse,
-                       (float*)dlogits, R, V, scale, ignore_index);
-  return hipGetLastError();
+  return ce_launch(R, V, is_bf16, [&](auto tag, dim3 grid, dim3 block) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((ce_bwd_kernel<T, Vec<T>::W>), grid, block, 0, stream,
+                       (const T*)logits, targets, lse, (T*)dlogits, R, V, scale,
+                       ignore_index);
+  });
 }
 
 }  // extern "C"

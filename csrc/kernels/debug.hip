@@ -7,6 +7,7 @@
 //               transposed) and reconstruct it through frag_read — validates
 //               the staging/swizzle/fragment-read path without MFMA.
 #include "common.h"
+#include "launchers.h"
 
 namespace tdsa {
 

@@ -6,40 +6,25 @@
 // backward sums each table row's contributions in fp32 in sorted-index order
 // (no atomics: the result is the same from run to run).
 #include "common.h"
+#include "launchers.h"
 
 namespace tdsa {
 
-// vector type of width W over T
-template <typename T, int W> struct VecOf;
-template <> struct VecOf<float, 4> { typedef float4v type; };
-template <> struct VecOf<bf16, 8> { typedef short8v type; };
-
-template <typename T>
-__global__ void emb_fwd_scalar(const T* __restrict__ weight,
+// Row gather, W elements per thread and step: the full 16-byte vector when
+// D is a whole number of them, else W = 1 (the launcher picks).
+template <typename T, int W>
+__global__ void emb_fwd_kernel(const T* __restrict__ weight,
                                const long long* __restrict__ idx,
                                T* __restrict__ out, long long R, int D) {
-  const long long total = R * D;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = global_tid(); i < total; i += stride) {
-    const long long r = i / D;
-    const int c = (int)(i % D);
-    out[i] = weight[idx[r] * (long long)D + c];
-  }
-}
-
-template <typename T, int W>
-__global__ void emb_fwd_vec(const T* __restrict__ weight,
-                            const long long* __restrict__ idx,
-                            T* __restrict__ out, long long R, int D) {
-  typedef typename VecOf<T, W>::type V;
+  using VT = Vec<T, W>;
   const int chunks = D / W;
   const long long total = R * chunks;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = global_tid(); i < total; i += stride) {
     const long long r = i / chunks;
     const int c = (int)(i % chunks) * W;
-    *reinterpret_cast<V*>(out + r * (long long)D + c) =
-        *reinterpret_cast<const V*>(weight + idx[r] * (long long)D + c);
+    VT::store(out + r * (long long)D + c,
+              VT::load(weight + idx[r] * (long long)D + c));
   }
 }
 
@@ -119,25 +104,18 @@ extern "C" {
 hipError_t tdsa_embedding_fwd(const void* weight, const long long* idx, void* out,
                               long long R, int D, int is_bf16, hipStream_t stream) {
   const int block = 256;
-  if (is_bf16 && D % 8 == 0) {
-    long long work = R * (D / 8);
-    hipLaunchKernelGGL((emb_fwd_vec<bf16, 8>), dim3(capped_grid(work, block)),
-                       dim3(block), 0, stream, (const bf16*)weight, idx,
-                       (bf16*)out, R, D);
-  } else if (!is_bf16 && D % 4 == 0) {
-    long long work = R * (D / 4);
-    hipLaunchKernelGGL((emb_fwd_vec<float, 4>), dim3(capped_grid(work, block)),
-                       dim3(block), 0, stream, (const float*)weight, idx,
-                       (float*)out, R, D);
-  } else if (is_bf16) {
-    hipLaunchKernelGGL(emb_fwd_scalar<bf16>, dim3(capped_grid(R * D, block)),
-                       dim3(block), 0, stream, (const bf16*)weight, idx,
-                       (bf16*)out, R, D);
-  } else {
-    hipLaunchKernelGGL(emb_fwd_scalar<float>, dim3(capped_grid(R * D, block)),
-                       dim3(block), 0, stream, (const float*)weight, idx,
-                       (float*)out, R, D);
-  }
+  dispatch_dtype(is_bf16, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr int W = Vec<T>::W;
+    if (D % W == 0)
+      hipLaunchKernelGGL((emb_fwd_kernel<T, W>),
+                         dim3(capped_grid(R * (D / W), block)), dim3(block), 0,
+                         stream, (const T*)weight, idx, (T*)out, R, D);
+    else
+      hipLaunchKernelGGL((emb_fwd_kernel<T, 1>),
+                         dim3(capped_grid(R * D, block)), dim3(block), 0,
+                         stream, (const T*)weight, idx, (T*)out, R, D);
+  });
   return hipGetLastError();
 }
 
@@ -149,14 +127,12 @@ hipError_t tdsa_embedding_bwd(const void* dy, const long long* idx,
                               long long R, int D, long long padding_idx,
                               int is_bf16, hipStream_t stream) {
   const int block = 256;
-  if (is_bf16)
-    hipLaunchKernelGGL(emb_bwd_kernel<bf16>, dim3(capped_grid(R * D, block)),
-                       dim3(block), 0, stream, (const bf16*)dy, idx, perm, dw32,
+  dispatch_dtype(is_bf16, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(emb_bwd_kernel<T>, dim3(capped_grid(R * D, block)),
+                       dim3(block), 0, stream, (const T*)dy, idx, perm, dw32,
                        part, R, D, padding_idx);
-  else
-    hipLaunchKernelGGL(emb_bwd_kernel<float>, dim3(capped_grid(R * D, block)),
-                       dim3(block), 0, stream, (const float*)dy, idx, perm, dw32,
-                       part, R, D, padding_idx);
+  });
   if (R > EMB_PIECE)
     hipLaunchKernelGGL(emb_bwd_join,
                        dim3(capped_grid(((R - 1) / EMB_PIECE) * D, block)),

@@ -26,6 +26,7 @@
 // Reference hot path being replaced:
 // /root/reference/tiny_deepspeed/core/module/ops/linear.py:59-68.
 #include "common.h"
+#include "launchers.h"
 #include "mfma.h"
 
 #include <cstdlib>

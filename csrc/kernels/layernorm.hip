@@ -9,28 +9,11 @@
 // (one wave per row, dw/db partials in registers); fp32 and wider rows on
 // the workgroup-per-row and wide kernels.
 #include "common.h"
+#include "launchers.h"
 
 #include <type_traits>
 
 namespace tdsa {
-
-template <typename T> struct VecTraits;
-template <> struct VecTraits<float> {
-  static constexpr int W = 4;
-  typedef float4v V;
-  static DEV_INLINE V load(const float* p) { return *reinterpret_cast<const V*>(p); }
-  static DEV_INLINE float get(V v, int i) { return v[i]; }
-  static DEV_INLINE void set(V& v, int i, float x) { v[i] = x; }
-  static DEV_INLINE void store(float* p, V v) { *reinterpret_cast<V*>(p) = v; }
-};
-template <> struct VecTraits<bf16> {
-  static constexpr int W = 8;
-  typedef short8v V;
-  static DEV_INLINE V load(const bf16* p) { return load8(p); }
-  static DEV_INLINE float get(V v, int i) { return bf_elem(v, i); }
-  static DEV_INLINE void set(V& v, int i, float x) { v[i] = bf_pack(x); }
-  static DEV_INLINE void store(bf16* p, V v) { store8(p, v); }
-};
 
 // ---- workgroup-per-row kernels (fp32, and bf16 with TDSA_LN_ROWWAVE=0) ------
 // Register-cache depth: a thread keeps up to LN_WG_MAXITER vectors of its row
@@ -54,7 +37,7 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res
                               const T* __restrict__ b, T* __restrict__ y,
                               float* __restrict__ mean, float* __restrict__ rstd,
                               int M, int N, float eps) {
-  using VT = VecTraits<T>;
+  using VT = Vec<T>;
   constexpr int W = VT::W;
   constexpr bool CACHED = MAXITER > 0;
   __shared__ float scratch[2 * 1024 / WAVE];
@@ -130,7 +113,7 @@ __global__ void ln_bwd_dx_kernel(const T* __restrict__ dy, const T* __restrict__
                                  const T* __restrict__ w, const float* __restrict__ mean,
                                  const float* __restrict__ rstd, T* __restrict__ dx,
                                  int M, int N) {
-  using VT = VecTraits<T>;
+  using VT = Vec<T>;
   constexpr int W = VT::W;
   __shared__ float scratch[2 * 1024 / WAVE];
   const int tid = threadIdx.x;
@@ -200,7 +183,7 @@ __global__ void ln_dwdb_accum_kernel(const T* __restrict__ dy,
                                      const float* __restrict__ rstd,
                                      float* __restrict__ pdw,
                                      float* __restrict__ pdb, int M, int N) {
-  using VT = VecTraits<T>;
+  using VT = Vec<T>;
   constexpr int W = VT::W;
   const int tid = threadIdx.x;
   const int nth = blockDim.x;
@@ -284,7 +267,7 @@ __global__ __launch_bounds__(LN_RW_BLOCK) void ln_fwd_rowwave_kernel(
     const T* __restrict__ w, const T* __restrict__ b, T* __restrict__ y,
     float* __restrict__ mean, float* __restrict__ rstd, int M, int N,
     float eps) {
-  using VT = VecTraits<T>;
+  using VT = Vec<T>;
   typedef typename VT::V V;
   constexpr int W = VT::W;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -387,7 +370,7 @@ __global__ __launch_bounds__(LN_RW_BLOCK) void ln_bwd_rowwave_kernel(
     const T* __restrict__ w, const float* __restrict__ mean,
     const float* __restrict__ rstd, T* __restrict__ dx,
     float* __restrict__ pdw, float* __restrict__ pdb, int M, int N) {
-  using VT = VecTraits<T>;
+  using VT = Vec<T>;
   typedef typename VT::V V;
   constexpr int W = VT::W;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -499,12 +482,12 @@ __global__ __launch_bounds__(LN_RW_BLOCK) void ln_bwd_rowwave_kernel(
       const unsigned col = voff + j * WAVE * W;
 #pragma unroll
       for (int k = 0; k < W; k += 4) {
-        float4v vw = {accdw[j][k], accdw[j][k + 1], accdw[j][k + 2],
+        f32x4 vw = {accdw[j][k], accdw[j][k + 1], accdw[j][k + 2],
                       accdw[j][k + 3]};
-        float4v vb = {accdb[j][k], accdb[j][k + 1], accdb[j][k + 2],
+        f32x4 vb = {accdb[j][k], accdb[j][k + 1], accdb[j][k + 2],
                       accdb[j][k + 3]};
-        *reinterpret_cast<float4v*>(sdw + col + k) = vw;
-        *reinterpret_cast<float4v*>(sdb + col + k) = vb;
+        *reinterpret_cast<f32x4*>(sdw + col + k) = vw;
+        *reinterpret_cast<f32x4*>(sdb + col + k) = vb;
       }
     }
   }
@@ -526,7 +509,7 @@ __global__ void ln_bwd_dx_wide_kernel(const T* __restrict__ dy,
                                       const float* __restrict__ rstd,
                                       T* __restrict__ dx, float* __restrict__ pdw,
                                       float* __restrict__ pdb, int M, int N) {
-  using VT = VecTraits<T>;
+  using VT = Vec<T>;
   constexpr int W = VT::W;
   __shared__ float scratch[2 * 1024 / WAVE];
   const int tid = threadIdx.x;
@@ -726,7 +709,7 @@ template <typename T>
 static hipError_t ln_fwd_wg(const T* x, const T* res, T* h, const T* w,
                             const T* b, T* y, float* mean, float* rstd, int M,
                             int N, float eps, hipStream_t stream) {
-  constexpr int W = VecTraits<T>::W;
+  constexpr int W = Vec<T>::W;
   if (N % W) return hipErrorInvalidValue;  // 16B row-base alignment
   const int block = ln_block(N, W);
   const int grid = ln_wg_grid(M);
@@ -751,7 +734,7 @@ static hipError_t ln_bwd_dx_wg(const T* dy, const T* dh, const T* x, const T* w,
                                const float* mean, const float* rstd, T* dx,
                                float* pdw, float* pdb, int M, int N,
                                hipStream_t stream) {
-  constexpr int W = VecTraits<T>::W;
+  constexpr int W = Vec<T>::W;
   if (N % W) return hipErrorInvalidValue;  // 16B row-base alignment
   const int block = ln_block(N, W);
   const int stripes = ln_stripe_count(M, 0);
@@ -809,12 +792,11 @@ hipError_t tdsa_ln_fwd(const void* x, const void* res, void* h, const void* w,
     });
     return hipGetLastError();
   }
-  if (is_bf16)
-    return ln_fwd_wg((const bf16*)x, (const bf16*)res, (bf16*)h, (const bf16*)w,
-                     (const bf16*)b, (bf16*)y, mean, rstd, M, N, eps, stream);
-  return ln_fwd_wg((const float*)x, (const float*)res, (float*)h,
-                   (const float*)w, (const float*)b, (float*)y, mean, rstd, M, N,
-                   eps, stream);
+  return dispatch_dtype(is_bf16, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return ln_fwd_wg((const T*)x, (const T*)res, (T*)h, (const T*)w,
+                     (const T*)b, (T*)y, mean, rstd, M, N, eps, stream);
+  });
 }
 
 // G (stripe count), reported to the caller so it can size pdw/pdb. This and
@@ -845,13 +827,11 @@ hipError_t tdsa_ln_bwd_dx(const void* dy, const void* dh, const void* x,
     });
     return hipGetLastError();
   }
-  if (is_bf16)
-    return ln_bwd_dx_wg((const bf16*)dy, (const bf16*)dh, (const bf16*)x,
-                        (const bf16*)w, mean, rstd, (bf16*)dx, pdw, pdb, M, N,
-                        stream);
-  return ln_bwd_dx_wg((const float*)dy, (const float*)dh, (const float*)x,
-                      (const float*)w, mean, rstd, (float*)dx, pdw, pdb, M, N,
-                      stream);
+  return dispatch_dtype(is_bf16, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return ln_bwd_dx_wg((const T*)dy, (const T*)dh, (const T*)x, (const T*)w,
+                        mean, rstd, (T*)dx, pdw, pdb, M, N, stream);
+  });
 }
 
 // out_bf16: write dw/db as bf16 (rounded once from the fp32 sums) instead
@@ -860,14 +840,11 @@ hipError_t tdsa_ln_bwd_dwdb(const float* pdw, const float* pdb, void* dw,
                             void* db, int G, int N, int out_bf16,
                             hipStream_t stream) {
   const int grid = (N + LN_DWDB_SLAB - 1) / LN_DWDB_SLAB;
-  if (out_bf16)
-    hipLaunchKernelGGL(ln_bwd_dwdb_kernel<bf16>, dim3(grid),
-                       dim3(LN_DWDB_BLOCK), 0, stream, pdw, pdb, (bf16*)dw,
-                       (bf16*)db, G, N);
-  else
-    hipLaunchKernelGGL(ln_bwd_dwdb_kernel<float>, dim3(grid),
-                       dim3(LN_DWDB_BLOCK), 0, stream, pdw, pdb, (float*)dw,
-                       (float*)db, G, N);
+  dispatch_dtype(out_bf16, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(ln_bwd_dwdb_kernel<T>, dim3(grid), dim3(LN_DWDB_BLOCK),
+                       0, stream, pdw, pdb, (T*)dw, (T*)db, G, N);
+  });
   return hipGetLastError();
 }
 

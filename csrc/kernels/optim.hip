@@ -8,22 +8,10 @@
 // reference's per-parameter step-count bug is fixed: `step` is the global
 // 1-based optimizer step.
 #include "common.h"
+#include "launchers.h"
 #include "optim_desc.h"
 
 namespace tdsa {
-
-// 4-wide element vectors for params/grads in either dtype.
-template <typename T> struct Vec4;
-template <> struct Vec4<float> {
-  typedef f32x4 V;
-  static DEV_INLINE float get(V v, int k) { return v[k]; }
-  static DEV_INLINE void set(V& v, int k, float x) { v[k] = x; }
-};
-template <> struct Vec4<bf16> {
-  typedef short4v V;
-  static DEV_INLINE float get(V v, int k) { return bf_elem(v, k); }
-  static DEV_INLINE void set(V& v, int k, float x) { v[k] = bf_pack(x); }
-};
 
 // One chunk [start, end) of one tensor under `rule`, with S fp32 state
 // streams `st`. 4 elements per lane with EXPLICIT dwordx4/dwordx2 accesses:
@@ -35,8 +23,11 @@ template <int S, bool HASM, typename Rule, typename PT, typename GT>
 DEV_INLINE void update_span(const Rule& rule, PT* p, const GT* g,
                             const typename Rule::Desc& d, float* const* st,
                             long long start, long long end) {
-  typedef typename Vec4<PT>::V PV;
-  typedef typename Vec4<GT>::V GV;
+  // params/grads 4 wide in either dtype, next to the fp32 state vectors
+  typedef Vec<PT, 4> PVec;
+  typedef Vec<GT, 4> GVec;
+  typedef typename PVec::V PV;
+  typedef typename GVec::V GV;
   float* const master = d.master;
   const long long n4 = (end - start) / 4;
   for (long long q = threadIdx.x; q < n4; q += blockDim.x) {
@@ -52,7 +43,7 @@ DEV_INLINE void update_span(const Rule& rule, PT* p, const GT* g,
     } else {
       const PV praw = *reinterpret_cast<const PV*>(p + i);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) pv[k] = Vec4<PT>::get(praw, k);
+      for (int k = 0; k < 4; ++k) pv[k] = PVec::get(praw, k);
     }
     PV pout;
 #pragma unroll
@@ -60,10 +51,10 @@ DEV_INLINE void update_span(const Rule& rule, PT* p, const GT* g,
       float s[S + 1];
 #pragma unroll
       for (int j = 0; j < S; ++j) s[j] = sv[j][k];
-      pv[k] = rule.template elem<S>(d, Vec4<GT>::get(gv, k), pv[k], s);
+      pv[k] = rule.template elem<S>(d, GVec::get(gv, k), pv[k], s);
 #pragma unroll
       for (int j = 0; j < S; ++j) sv[j][k] = s[j];
-      Vec4<PT>::set(pout, k, pv[k]);
+      PVec::set(pout, k, pv[k]);
     }
 #pragma unroll
     for (int j = 0; j < S; ++j) *reinterpret_cast<f32x4*>(st[j] + i) = sv[j];

@@ -973,3 +973,134 @@ def test_adamw_multi_rejects_bad_entry_gpu(bad):
     torch.cuda.synchronize()
     for t, b in zip(ps + ms + vs, before):
         assert torch.equal(t, b)
+
+
+# ---- argument checks of the LayerNorm / pointwise / CE / embedding bindings --
+def _binding_call(op):
+    """(argument names, valid arguments, check of the valid call's result)
+    for one binding, at a few dozen elements."""
+    import importlib
+    ce = importlib.import_module("tiny_deepspeed_amd.ops.cross_entropy")
+    emb = importlib.import_module("tiny_deepspeed_amd.ops.embedding")
+    gelu = importlib.import_module("tiny_deepspeed_amd.ops.gelu")
+    ln = importlib.import_module("tiny_deepspeed_amd.ops.layernorm")
+
+    g = torch.Generator().manual_seed(0)
+
+    def rnd(*shape):
+        return torch.randn(*shape, generator=g).cuda()
+
+    x, dy, res, w, b = rnd(4, 8), rnd(4, 8), rnd(4, 8), rnd(8), rnd(8)
+    if op == "layernorm_fwd":
+        def check(out):
+            y_ref = torch.nn.functional.layer_norm(x + res, (8,), w, b)
+            _close(out[0], y_ref, 1e-5, op)
+            _close(out[3], x + res, 1e-6, op + " h")
+        return ["x", "w", "b", "eps", "res"], [x, w, b, 1e-5, res], check
+    if op == "layernorm_bwd_dx":
+        _, mean, rstd = ln.ln_fwd_torch(x, w, b, 1e-5)
+        dh = rnd(4, 8)
+        ref, _ = ln.ln_dx_torch(dy, x, w, mean, rstd, dh)
+        return (["dy", "x", "w", "mean", "rstd", "dh"],
+                [dy, x, w, mean, rstd, dh],
+                lambda out: _close(out[0], ref, 1e-5, op))
+    if op == "gelu_bwd":
+        ref = gelu.gelu_bwd_torch(dy, x)
+        return ["dy", "x"], [dy, x], lambda out: _close(out, ref, 1e-5, op)
+    if op == "column_sum":
+        return ["dy"], [dy], lambda out: _close(out, dy.sum(0), 1e-6, op)
+    idx = torch.tensor([[1, 6, 1], [0, 3, 1]], device="cuda")
+    table = rnd(7, 4)
+    if op == "embedding_fwd":
+        return (["weight", "idx"], [table, idx.view(-1)],
+                lambda out: torch.equal(out, table[idx.view(-1)]) or
+                pytest.fail("embedding_fwd after a rejected call"))
+    if op == "embedding_bwd":
+        demb = rnd(6, 4)
+        ref = emb.emb_bwd_torch(idx.view(-1), demb, 7, None)
+        return (["dy", "idx", "num_embeddings", "padding_idx"],
+                [demb, idx.view(-1), 7, -1],
+                lambda out: _close(out, ref, 1e-6, op))
+    logits = rnd(4, 8)
+    targets = torch.tensor([0, 7, -100, 3], device="cuda")
+    loss_ref, lse_ref, n_ref = ce.ce_fwd_torch(logits, targets, -100)
+    if op == "cross_entropy_fwd":
+        def check(out):
+            _close(out[0], loss_ref, 1e-6, op)
+            _close(out[1], lse_ref, 1e-6, op + " lse")
+            assert int(out[2]) == int(n_ref) == 3
+        return (["logits", "targets", "ignore_index"], [logits, targets, -100],
+                check)
+    assert op == "cross_entropy_bwd"
+    ref = ce.ce_bwd_torch(1.0, logits, targets, lse_ref, 3, -100)
+    return (["logits", "targets", "lse", "dloss", "n_valid", "ignore_index"],
+            [logits, targets, lse_ref, 1.0, 3, -100],
+            lambda out: _close(out, ref, 1e-6, op))
+
+
+_BAD = {
+    "bf16": lambda t: t.to(torch.bfloat16),
+    "f64": lambda t: t.double(),
+    "i32": lambda t: t.int(),
+    "one_short": lambda t: t.reshape(-1)[:-1].clone(),
+    "one_row_short": lambda t: t[:-1].contiguous(),
+    "strided": lambda t: t.t(),
+    "cpu": lambda t: t.cpu(),
+    "rank1": lambda t: t.reshape(-1),
+    "rank3": lambda t: t.unsqueeze(0),
+    # no elements, so no memory: a width / a row count past INT_MAX
+    "wide": lambda t: torch.empty(0, 2 ** 31, device="cuda", dtype=t.dtype),
+    "tall": lambda t: torch.empty(2 ** 31, 0, device="cuda", dtype=t.dtype),
+}
+
+
+# (binding, the one bad argument, what is wrong with it, name in the message)
+@pytest.mark.parametrize("op,arg,bad,named", [
+    ("layernorm_fwd", "w", "bf16", "w"),
+    ("layernorm_fwd", "b", "bf16", "b"),
+    ("layernorm_fwd", "w", "one_short", "w"),
+    ("layernorm_fwd", "b", "one_short", "b"),
+    ("layernorm_fwd", "res", "bf16", "res"),
+    ("layernorm_fwd", "res", "one_short", "res"),
+    ("layernorm_fwd", "x", "strided", "x"),
+    ("layernorm_fwd", "w", "cpu", "w"),
+    ("layernorm_bwd_dx", "dy", "bf16", "dy"),
+    ("layernorm_bwd_dx", "dy", "strided", "dy"),
+    ("layernorm_bwd_dx", "w", "bf16", "w"),
+    ("layernorm_bwd_dx", "w", "one_short", "w"),
+    ("layernorm_bwd_dx", "mean", "one_short", "mean"),
+    ("layernorm_bwd_dx", "rstd", "one_short", "rstd"),
+    ("layernorm_bwd_dx", "rstd", "f64", "rstd"),
+    ("layernorm_bwd_dx", "dh", "bf16", "dh"),
+    ("layernorm_bwd_dx", "dh", "cpu", "dh"),
+    ("gelu_bwd", "dy", "one_short", "dy"),
+    ("gelu_bwd", "dy", "bf16", "dy"),
+    ("column_sum", "dy", "strided", "dy"),
+    ("column_sum", "dy", "wide", "N"),
+    ("column_sum", "dy", "tall", "M"),
+    ("embedding_fwd", "weight", "rank1", "weight"),
+    ("embedding_fwd", "weight", "wide", "D"),
+    ("embedding_fwd", "idx", "i32", "idx"),
+    ("embedding_fwd", "idx", "cpu", "idx"),
+    ("embedding_bwd", "dy", "one_row_short", "dy"),
+    ("embedding_bwd", "idx", "i32", "idx"),
+    ("cross_entropy_fwd", "targets", "one_short", "targets"),
+    ("cross_entropy_fwd", "targets", "i32", "targets"),
+    ("cross_entropy_fwd", "logits", "strided", "logits"),
+    ("cross_entropy_bwd", "logits", "rank3", "logits"),
+    ("cross_entropy_bwd", "targets", "one_short", "targets"),
+    ("cross_entropy_bwd", "lse", "one_short", "lse"),
+    ("cross_entropy_bwd", "lse", "f64", "lse"),
+])
+def test_bindings_reject_bad_arguments_gpu(op, arg, bad, named):
+    """One bad argument per case: the binding names itself and the argument
+    and launches nothing; the same call with valid arguments, next on the
+    stream, then gives the right answer."""
+    fn = getattr(_ext.get_ext(), op)
+    names, good, check = _binding_call(op)
+    args = list(good)
+    args[names.index(arg)] = _BAD[bad](good[names.index(arg)])
+    with pytest.raises(RuntimeError, match=rf"{op}: {named}\b"):
+        fn(*args)
+    check(fn(*good))
+    torch.cuda.synchronize()

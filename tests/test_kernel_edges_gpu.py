@@ -129,8 +129,9 @@ def test_column_sum_edges_gpu(dtype, cap, M, N):
 
 
 # ---- embedding ---------------------------------------------------------------
-# D = 12 takes the scalar path in bf16 (12 % 8 != 0), the vector path in fp32
-@pytest.mark.parametrize("D", [8, 12, 768])
+# D = 12 takes the scalar path in bf16 (12 % 8 != 0), the vector path in fp32;
+# D = 6 the scalar path in both (6 % 4 != 0)
+@pytest.mark.parametrize("D", [6, 8, 12, 768])
 @pytest.mark.parametrize("dtype", [BF16, F32])
 def test_embedding_fwd_edges_gpu(dtype, D):
     V = 97

@@ -15,6 +15,8 @@ import time
 
 import torch
 
+from . import _ext
+
 
 class RuntimeAutoTuner:
     def __init__(self, enabled: bool = True, warmup: int = 5, iters: int = 20):
@@ -147,3 +149,19 @@ def default_tuner():
 
                 atexit.register(_save)
     return _DEFAULT_TUNER
+
+
+def dispatch(op_name, candidates, args, on, tuner=None, supported=True):
+    """The one choice every tuned {HIP kernel, torch} op makes. candidates is
+    [hip, torch]; `on` is the tensor whose device decides; `supported` is the
+    op's own "the kernel takes this shape" test. Without a native extension
+    for `on`, or with an unsupported shape, the torch candidate runs and the
+    tuner never sees the call. Otherwise the tuner (the given one, else the
+    process default) picks; without a tuner the HIP kernel runs."""
+    hip, composite = candidates
+    if not (_ext.use_native(on) and supported):
+        return composite(*args)
+    tuner = tuner if tuner is not None else default_tuner()
+    if tuner is not None:
+        return tuner.choose(op_name, candidates, *args)
+    return hip(*args)

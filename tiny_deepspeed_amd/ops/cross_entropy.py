@@ -12,7 +12,7 @@ Dispatch is {CDNA4 kernel, torch composite} through the runtime autotuner
 import torch
 
 from . import _ext
-from .autotuner import default_tuner
+from .autotuner import dispatch
 
 
 def _kernel_supported(logits2d):
@@ -42,13 +42,9 @@ def ce_fwd_torch(logits2d, targets, ignore_index):
 
 def cross_entropy_fwd(logits2d, targets, ignore_index=-100, tuner=None):
     """Returns (loss_sum[fp32 scalar], lse[rows fp32], n_valid[int64 scalar])."""
-    if not (_ext.use_native(logits2d) and _kernel_supported(logits2d)):
-        return ce_fwd_torch(logits2d, targets, ignore_index)
-    tuner = tuner if tuner is not None else default_tuner()
-    if tuner is not None:
-        return tuner.choose("ce_fwd", [ce_fwd_hip, ce_fwd_torch],
-                            logits2d, targets, ignore_index)
-    return ce_fwd_hip(logits2d, targets, ignore_index)
+    return dispatch("ce_fwd", [ce_fwd_hip, ce_fwd_torch],
+                    (logits2d, targets, ignore_index), logits2d, tuner,
+                    _kernel_supported(logits2d))
 
 
 def ce_bwd_hip(dloss, logits2d, targets, lse, n_valid, ignore_index, out=None):
@@ -78,16 +74,9 @@ def cross_entropy_bwd(dloss, logits2d, targets, lse, n_valid,
                       ignore_index=-100, tuner=None, out=None):
     """out: optional pre-allocated dlogits destination (e.g. a row-slice of
     the fused lm_head+CE full-dlogits buffer) — skips an extra copy."""
-    if not (_ext.use_native(logits2d) and _kernel_supported(logits2d)):
-        return ce_bwd_torch(dloss, logits2d, targets, lse, n_valid,
-                            ignore_index, out)
-    tuner = tuner if tuner is not None else default_tuner()
-    if tuner is not None:
-        return tuner.choose("ce_bwd", [ce_bwd_hip, ce_bwd_torch],
-                            dloss, logits2d, targets, lse, n_valid,
-                            ignore_index, out)
-    return ce_bwd_hip(dloss, logits2d, targets, lse, n_valid, ignore_index,
-                      out)
+    return dispatch("ce_bwd", [ce_bwd_hip, ce_bwd_torch],
+                    (dloss, logits2d, targets, lse, n_valid, ignore_index, out),
+                    logits2d, tuner, _kernel_supported(logits2d))
 
 
 class _CrossEntropyFn(torch.autograd.Function):

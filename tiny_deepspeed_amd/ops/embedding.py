@@ -13,7 +13,7 @@ identical from run to run), converted to the param dtype at the end. padding_idx
 import torch
 
 from . import _ext
-from .autotuner import default_tuner
+from .autotuner import dispatch
 
 
 def emb_fwd_hip(weight, idx, padding_idx=None):
@@ -27,13 +27,8 @@ def emb_fwd_torch(weight, idx, padding_idx=None):
 
 
 def embedding_forward(weight, idx, padding_idx=None, tuner=None):
-    if not _ext.use_native(weight):
-        return emb_fwd_torch(weight, idx, padding_idx)
-    tuner = tuner if tuner is not None else default_tuner()
-    if tuner is not None:
-        return tuner.choose("emb_fwd", [emb_fwd_hip, emb_fwd_torch],
-                            weight, idx, padding_idx)
-    return emb_fwd_hip(weight, idx, padding_idx)
+    return dispatch("emb_fwd", [emb_fwd_hip, emb_fwd_torch],
+                    (weight, idx, padding_idx), weight, tuner)
 
 
 def emb_bwd_hip(flat_idx, dy2, num_embeddings, padding_idx):
@@ -58,10 +53,5 @@ def emb_bwd_torch(flat_idx, dy2, num_embeddings, padding_idx):
 def embedding_weight_grad(idx, dy, num_embeddings, padding_idx=None, tuner=None):
     flat_idx = idx.reshape(-1)
     dy2 = dy.reshape(-1, dy.shape[-1])
-    if not _ext.use_native(dy2):
-        return emb_bwd_torch(flat_idx, dy2, num_embeddings, padding_idx)
-    tuner = tuner if tuner is not None else default_tuner()
-    if tuner is not None:
-        return tuner.choose("emb_bwd", [emb_bwd_hip, emb_bwd_torch],
-                            flat_idx, dy2, num_embeddings, padding_idx)
-    return emb_bwd_hip(flat_idx, dy2, num_embeddings, padding_idx)
+    return dispatch("emb_bwd", [emb_bwd_hip, emb_bwd_torch],
+                    (flat_idx, dy2, num_embeddings, padding_idx), dy2, tuner)

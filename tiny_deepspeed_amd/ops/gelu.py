@@ -12,7 +12,7 @@ import math
 import torch
 
 from . import _ext
-from .autotuner import default_tuner
+from .autotuner import dispatch
 
 _C0 = math.sqrt(2.0 / math.pi)
 _C1 = 0.044715
@@ -29,12 +29,7 @@ def gelu_fwd_torch(x):
 
 
 def gelu_fwd(x, tuner=None):
-    if not _ext.use_native(x):
-        return gelu_fwd_torch(x)
-    tuner = tuner if tuner is not None else default_tuner()
-    if tuner is not None:
-        return tuner.choose("gelu_fwd", [gelu_fwd_hip, gelu_fwd_torch], x)
-    return gelu_fwd_hip(x)
+    return dispatch("gelu_fwd", [gelu_fwd_hip, gelu_fwd_torch], (x,), x, tuner)
 
 
 def gelu_bwd_hip(dy, x):
@@ -51,12 +46,8 @@ def gelu_bwd_torch(dy, x):
 
 
 def gelu_bwd(dy, x, tuner=None):
-    if not _ext.use_native(dy):
-        return gelu_bwd_torch(dy, x)
-    tuner = tuner if tuner is not None else default_tuner()
-    if tuner is not None:
-        return tuner.choose("gelu_bwd", [gelu_bwd_hip, gelu_bwd_torch], dy, x)
-    return gelu_bwd_hip(dy, x)
+    return dispatch("gelu_bwd", [gelu_bwd_hip, gelu_bwd_torch], (dy, x), dy,
+                    tuner)
 
 
 class _GeluFn(torch.autograd.Function):

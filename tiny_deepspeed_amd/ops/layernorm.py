@@ -22,7 +22,7 @@ winner cached. CPU uses the torch fp32 reference (also the test oracle).
 import torch
 
 from . import _ext
-from .autotuner import default_tuner
+from .autotuner import dispatch
 
 
 # --- forward candidates ----------------------------------------------------
@@ -42,13 +42,8 @@ def ln_fwd_torch(x, weight, bias, eps):
 
 def layernorm_fwd(x, weight, bias, eps=1e-5, tuner=None):
     """Returns (y, mean, rstd); mean/rstd are fp32 per-row tensors."""
-    if not _ext.use_native(x):
-        return ln_fwd_torch(x, weight, bias, eps)
-    tuner = tuner if tuner is not None else default_tuner()
-    if tuner is not None:
-        return tuner.choose("ln_fwd", [ln_fwd_hip, ln_fwd_torch],
-                            x, weight, bias, eps)
-    return ln_fwd_hip(x, weight, bias, eps)
+    return dispatch("ln_fwd", [ln_fwd_hip, ln_fwd_torch],
+                    (x, weight, bias, eps), x, tuner)
 
 
 def ln_fwd_res_hip(x, res, weight, bias, eps):
@@ -68,13 +63,8 @@ def layernorm_fwd_res(x, res, weight, bias, eps=1e-5, tuner=None):
     """Fused residual + LayerNorm: h = x + res; y = LN(h).
     Returns (h, y, mean, rstd) — h is the residual stream, written once by
     the kernel instead of a separate elementwise add pass."""
-    if not _ext.use_native(x):
-        return ln_fwd_res_torch(x, res, weight, bias, eps)
-    tuner = tuner if tuner is not None else default_tuner()
-    if tuner is not None:
-        return tuner.choose("ln_fwd_res", [ln_fwd_res_hip, ln_fwd_res_torch],
-                            x, res, weight, bias, eps)
-    return ln_fwd_res_hip(x, res, weight, bias, eps)
+    return dispatch("ln_fwd_res", [ln_fwd_res_hip, ln_fwd_res_torch],
+                    (x, res, weight, bias, eps), x, tuner)
 
 
 # --- backward-dx candidates ------------------------------------------------
@@ -104,13 +94,8 @@ def layernorm_dx(dy, x, weight, mean, rstd, dh=None, tuner=None):
     On the HIP path this also produces stripe partials for dw/db (returned
     as an opaque workspace consumed by layernorm_dwdb; the torch candidate
     returns the saved tensors for recompute instead — both accepted)."""
-    if not _ext.use_native(dy):
-        return ln_dx_torch(dy, x, weight, mean, rstd, dh)
-    tuner = tuner if tuner is not None else default_tuner()
-    if tuner is not None:
-        return tuner.choose("ln_dx", [ln_dx_hip, ln_dx_torch],
-                            dy, x, weight, mean, rstd, dh)
-    return ln_dx_hip(dy, x, weight, mean, rstd, dh)
+    return dispatch("ln_dx", [ln_dx_hip, ln_dx_torch],
+                    (dy, x, weight, mean, rstd, dh), dy, tuner)
 
 
 def layernorm_dwdb(workspace, dtype=None, tuner=None):

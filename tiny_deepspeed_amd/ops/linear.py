@@ -24,7 +24,7 @@ import os
 import torch
 
 from . import _ext
-from .autotuner import default_tuner
+from .autotuner import default_tuner, dispatch
 
 
 def _flatten_batch(t):
@@ -94,9 +94,4 @@ def db_torch(dy2):
 
 def linear_bias_grad(dy, tuner=None):
     dy2 = _flatten_batch(dy)
-    if not _ext.use_native(dy2):
-        return db_torch(dy2)
-    tuner = tuner if tuner is not None else default_tuner()
-    if tuner is not None:
-        return tuner.choose("linear_db", [db_hip, db_torch], dy2)
-    return db_hip(dy2)
+    return dispatch("linear_db", [db_hip, db_torch], (dy2,), dy2, tuner)
