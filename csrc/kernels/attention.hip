@@ -20,8 +20,9 @@
 //             The 1/sqrt(D) on dS is folded into the dK/dQ epilogue.
 //
 // The three kernels share one skeleton: BlockCtx (block prologue), TilePipe
-// (two-tile LDS pipeline), FragOff (fragment read offsets), frag_from_packed
-// (C -> A repack) and store_ctiles (epilogue).
+// (two-tile LDS pipeline; in the dkv kernel its companion RowPipe carries
+// lse and delta of the next Q tile along), FragOff (fragment read offsets),
+// frag_from_packed (C -> A repack) and store_ctiles (epilogue).
 //
 // All global accesses are stride-parameterized so the kernels consume the
 // packed qkv projection layout (B,T,3,H,D) and write O/dQKV into (B,T,H,D)
@@ -30,7 +31,19 @@
 // VALU discipline (first profile measured 22:1 VALU:MFMA on a naive
 // version): every LDS offset is precomputed before the K/V loop; causal
 // masking runs only on diagonal tiles (wave-uniform branch); waves whose
-// rows lie entirely outside a tile skip its compute.
+// rows lie entirely outside a tile skip its compute. Two bf16 results that
+// share a word are packed by ONE v_cvt_pk_bf16_f32 (pack2, mfma.h). Per
+// off-diagonal tile and wave the 8-wave loops issue about 155 (fwd, 16
+// MFMA; 19 more when the running max moves), 125 (dq, 24 MFMA) and 150
+// (dkv, 32 MFMA) vector instructions (profiles/attn_valu.txt);
+// what is left is the softmax itself (sub, exp2, max/sum, the P*(dP-delta)
+// products), the permlane repack and LDS addressing.
+//
+// Waits: each loop waits for global memory once per tile, at its head, for
+// loads issued a whole tile earlier. The dkv kernel fetches lse/delta of
+// tile i+1 together with tile i+1's Q/dO (RowPipe) for that reason: loads
+// retire in order, and a load-and-use between the prefetch and the barrier
+// would wait for the prefetch as well.
 //
 // 32x32x16 fragment layouts (hardware-verified slot-pairing rule: A and B
 // must agree on the slot->k map, C is fixed; see scripts/debug_mfma.py):
@@ -61,6 +74,12 @@ DEV_INLINE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 // Raw v_rcp_f32 for the epilogue 1/l (IEEE div emits ~10-inst div_scale
 // chains; the result feeds a bf16 store).
 DEV_INLINE float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+// Value barrier (emits nothing): the compiler may not look through x. Used
+// where it otherwise rewrites the dropout code into something costlier:
+// a select moved across the bf16 pack (then done per half and re-joined with
+// v_perm_b32), or a per-tile index term folded into 32 hoisted registers.
+DEV_INLINE float pin(float x) { asm("" : "+v"(x)); return x; }
+DEV_INLINE unsigned pin(unsigned x) { asm("" : "+v"(x)); return x; }
 
 // XCD-aware block remap (T1): the dispatcher places linear block b on XCD
 // b % 8, and the x-dimension varies fastest, so the gridDim.x blocks that
@@ -129,8 +148,10 @@ struct FragOff {
 // Two-tile LDS pipeline: a pair of [64][64] tiles is staged per iteration,
 // with the next pair's global loads in flight under this pair's compute.
 //   prime();
-//   for (...) { next(lds_a, lds_b, more); <other LDS fills>; __syncthreads();
+//   for (...) { next(lds_a, lds_b, more); __syncthreads();
 //               <compute on lds_a / lds_b> }
+// Per-tile side inputs ride along as a companion (RowPipe, below), so that
+// no load-and-use sits between next() and the barrier.
 template <int NT>
 struct TilePipe {
   Stage<NT> a, b;
@@ -149,15 +170,71 @@ struct TilePipe {
   // with `more` the loads of the following pair. The caller places the
   // barrier that publishes the tiles.
   DEV_INLINE void next(char* lds_a, char* lds_b, bool more) {
+    next(lds_a, lds_b, more, NoRows{});
+  }
+
+  // The same with a companion (RowPipe) that rides along: its pending
+  // registers go to LDS after the tiles', its loads are issued after the
+  // tiles'. Every wait in here is for loads issued a whole iteration
+  // earlier; nothing waits between the new loads and the caller's barrier.
+  template <typename Rows>
+  DEV_INLINE void next(char* lds_a, char* lds_b, bool more, Rows&& rows) {
     __syncthreads();
     a.put(lds_a, pend_a);
     b.put(lds_b, pend_b);
+    rows.put();
     if (more) {
       a.advance();
       b.advance();
       a.fetch(pend_a);
       b.fetch(pend_b);
+      rows.advance();
+      rows.fetch();
     }
+  }
+
+  struct NoRows {
+    DEV_INLINE void put() {}
+    DEV_INLINE void advance() {}
+    DEV_INLINE void fetch() {}
+  };
+};
+
+// TilePipe companion for two fp32 values per tile row (lse and delta in the
+// dkv kernel), KVB rows per tile: thread r < KVB (wave 0) carries row r one
+// tile ahead in two registers and publishes a[r] * mul_a and b[r] to LDS.
+//   pipe.prime(); rows.fetch();
+//   for (...) { pipe.next(lds_a, lds_b, more, rows); __syncthreads(); ... }
+struct RowPipe {
+  const float* ga;   // the pending tile's first row (block-uniform)
+  const float* gb;
+  float* lds_a;
+  float* lds_b;
+  float mul_a;
+  int tid;
+  float pend_a, pend_b;
+
+  DEV_INLINE RowPipe(const float* ga, const float* gb, float* lds_a,
+                     float* lds_b, float mul_a, int tid)
+      : ga(ga), gb(gb), lds_a(lds_a), lds_b(lds_b), mul_a(mul_a), tid(tid) {}
+
+  DEV_INLINE void fetch() {
+    if (tid < KVB) {
+      pend_a = ga[tid];
+      pend_b = gb[tid];
+    }
+  }
+
+  DEV_INLINE void put() {
+    if (tid < KVB) {
+      lds_a[tid] = pend_a * mul_a;
+      lds_b[tid] = pend_b;
+    }
+  }
+
+  DEV_INLINE void advance() {
+    ga += KVB;
+    gb += KVB;
   }
 };
 
@@ -352,7 +429,7 @@ __global__ void attn_fwd_kernel(const bf16* __restrict__ q,
           psum += pe;
           if (DROP) {
             const int key = key0 + t2 * 32 + crow(4 * r1 + e, c.h32);
-            pe = drop.keep(drop_base + key) ? pe * drop.inv_keep : 0.f;
+            pe = pin(drop.keep(drop_base + key) ? pe * drop.inv_keep : 0.f);
           }
           p[e] = pe;
         }
@@ -452,19 +529,23 @@ __global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
   f32x16 dk_acc[2] = {};
   f32x16 dv_acc[2] = {};
 
+  // lse (to log2 space) and delta of each Q tile travel one tile ahead,
+  // next to the tile itself
+  const long long row0 = c.bh * T + i0 * KVB;
+  RowPipe rows(lse + row0, delta + row0, lds_lse, lds_dlt, LOG2E, c.tid);
   pipe.prime();
+  rows.fetch();
   for (int i = i0; i < T / KVB; ++i) {
-    pipe.next(lds_q, lds_do, i + 1 < T / KVB);
-    if (c.tid < KVB) {
-      lds_lse[c.tid] = lse[c.bh * T + i * KVB + c.tid] * LOG2E;
-      lds_dlt[c.tid] = delta[c.bh * T + i * KVB + c.tid];
-    }
+    pipe.next(lds_q, lds_do, i + 1 < T / KVB, rows);
     __syncthreads();
 
     const int q0 = i * KVB;
     if (q0 + KVB - 1 < key_lo) continue;
 
     const bool diag = q0 < key_lo + 32;
+    const int mask_lo = key_me - q0 - 4 * c.h32;  // diagonal tiles only
+    const unsigned drop_rowT =
+        DROP ? pin((unsigned)((q0 + 4 * c.h32) * T)) : 0;
     PackedC P, dS;
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {
@@ -491,12 +572,18 @@ __global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
             const int r = 4 * r1 + e;
             const int lrow = t2 * 32 + crow(r, c.h32);
             float pp = fast_exp2(s_acc[r] - lds_lse[lrow]);
-            if (MASK.value) pp = (key_me <= q0 + lrow) ? pp : 0.f;
+            // key_me <= q0 + lrow, with the lane's part of lrow moved into
+            // mask_lo: the compare is against a literal, where the first
+            // form kept one hoisted register per r live across the loop
+            if (MASK.value) pp = (t2 * 32 + crow(r, 0) >= mask_lo) ? pp : 0.f;
             float pv = pp;                 // masked/rescaled P feeds dV
             float dpv = dp_acc[r];         // masked/rescaled dP feeds dS
             if (DROP) {
+              // (q0 + lrow) * T, split like the mask: lane part + uniform
               const bool keep = drop.keep(
-                  drop_bhTT + (unsigned)((q0 + lrow) * T) + key_me);
+                  drop_bhTT +
+                  (drop_rowT + (unsigned)((t2 * 32 + crow(r, 0)) * T)) +
+                  key_me);
               pv = keep ? pp * drop.inv_keep : 0.f;
               dpv = keep ? dpv * drop.inv_keep : 0.f;
             }

@@ -31,10 +31,17 @@ DEV_INLINE int swz(int row, int byte_in_row) {
   return row * 128 + (byte_in_row ^ ((row & 7) << 4));
 }
 
+// Two floats -> one word of two bf16 (lo in bits 0-15), round-to-nearest-even
+// as __float2bfloat16. The 2-wide vector conversion is ONE v_cvt_pk_bf16_f32;
+// two scalar conversions joined through a union came out as two of them (one
+// lane unused each) plus a shift and an SDWA or.
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v;
+
 DEV_INLINE unsigned pack2(float lo, float hi) {
-  union { struct { short a, b; } s; unsigned u; } u;
-  u.s.a = bf_pack(lo);
-  u.s.b = bf_pack(hi);
+  const f32x2 f = {lo, hi};
+  union { bf16x2v h; unsigned u; } u;
+  u.h = __builtin_convertvector(f, bf16x2v);
   return u.u;
 }
 
