@@ -22,7 +22,20 @@
 // The three kernels share one skeleton: BlockCtx (block prologue), TilePipe
 // (two-tile LDS pipeline; in the dkv kernel its companion RowPipe carries
 // lse and delta of the next Q tile along), FragOff (fragment read offsets),
-// frag_from_packed (C -> A repack) and store_ctiles (epilogue).
+// frag_from_packed (C -> A repack) and store_ctiles (epilogue). Each kernel
+// is a pass loop around its attn_*_tile function.
+//
+// Workgroup -> tile mapping (tile_map, TDSA_ATTN_BALANCE): under the causal
+// mask tile t of n costs t+1 tiles of K/V (fwd, dq) or n-t tiles of Q (dkv).
+// A workgroup runs the pair (t, n-1-t) of one (batch, head), n+1 tiles
+// whichever pair; where the halved grid would not fill the device, one tile
+// as before, the heaviest tiles of the whole grid dispatched first. H=16,
+// T=1024, B=32: forward 167-171 -> 138-145 us, backward 538-547 -> 394-400 us
+// (profiles/attn_balance.txt).
+//
+// Epilogues: a lane holds one column of its wave's result, so o, dq, dk and
+// dv go through a per-wave LDS image and leave as whole 128-byte rows (16
+// bytes per lane, 4 store instructions per 32x64 tile instead of 32).
 //
 // All global accesses are stride-parameterized so the kernels consume the
 // packed qkv projection layout (B,T,3,H,D) and write O/dQKV into (B,T,H,D)
@@ -101,19 +114,70 @@ struct GStride {
   int t;
 };
 
+// Workgroup -> tile mapping (TDSA_ATTN_BALANCE). Under the causal mask tile t
+// of n costs t+1 units in fwd/dq and n-t in dkv, so BAL_OFF hands out
+// workgroups of 1..n units. BAL_PAIRS gives one workgroup the tiles t and
+// n-1-t of one (batch, head), one after the other: every workgroup then
+// costs n+1 units (the middle tile of an odd n runs alone).
+constexpr int BAL_OFF = 0;    // one tile per workgroup, x = tile
+constexpr int BAL_PAIRS = 1;  // two tiles per workgroup, x = pair
+constexpr int BAL_HEAVY = 2;  // one tile, heaviest tiles of the GRID first
+
 // Block prologue of all three kernels: the remapped (tile, batch*head) this
 // block owns and the lane's place in its wave's 32x32 MFMA tiles.
 struct BlockCtx {
   int tile;        // block index along T after the XCD remap
+  int tile2;       // BAL_PAIRS: the tile of the second pass, else -1
   long long bh;    // batch * H + head
   int tid, lane, w;
   int x32, h32;    // lane % 32 (index on the 32-axis), lane / 32
 
-  DEV_INLINE BlockCtx() {
+  // n_tiles: blocks along T; heavy_last: the cost grows with the tile index
+  DEV_INLINE BlockCtx(int n_tiles, int balance, bool heavy_last) {
     tile = blockIdx.x;
+    tile2 = -1;
     bh = blockIdx.y;
-    xcd_remap(gridDim.x, gridDim.y, tile, bh);
+    if (balance == BAL_HEAVY) {
+      const long long id = bh * gridDim.x + tile;   // linear dispatch id
+      const int rank = (int)(id / gridDim.y);
+      bh = id % gridDim.y;   // gridY % 8 == 0: a head stays on one XCD
+      tile = heavy_last ? n_tiles - 1 - rank : rank;
+    } else {
+      xcd_remap(gridDim.x, gridDim.y, tile, bh);
+      if (balance == BAL_PAIRS) {
+        // heavier tile first: the lighter one then finds its K/V (Q/dO) in L2
+        const int far = n_tiles - 1 - tile;
+        if (far != tile) tile2 = heavy_last ? tile : far;
+        if (heavy_last) tile = far;
+      }
+    }
+    place_lane();
+  }
+
+  // BAL_PAIRS: moves on to the second tile; false when there is none
+  DEV_INLINE bool next_pass() {
+    if (tile2 < 0) return false;
+    tile = tile2;
+    tile2 = -1;
+    place_lane();
+    return true;
+  }
+
+  // The lane's place, as values made anew for every pass and for every
+  // epilogue (fresh_lane): they are the same each time, and so is every
+  // fragment, staging and store offset derived from them. Left visible, the
+  // compiler computes all of those before the first pass and keeps them in
+  // registers through both (the 32 two-byte store offsets of the old
+  // epilogue alone were 64 VGPRs; the forward spilled 432 B).
+  DEV_INLINE BlockCtx fresh_lane() const {
+    BlockCtx e = *this;
+    e.place_lane();
+    return e;
+  }
+
+  DEV_INLINE void place_lane() {
     tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
     lane = tid & (WAVE - 1);
     w = tid / WAVE;
     x32 = lane & 31;
@@ -307,14 +371,45 @@ DEV_INLINE bfrag load_frag(const bf16* p, int row, int col, int st) {
 // Epilogue of one wave's 32x64 result, held as two C tiles: element
 // (crow(r,h32), 32*dt + x32) = acc[dt][r] * mul(r), stored as bf16 at row
 // stride st from p (the wave's first row).
+//
+// A lane holds one column of the tile, so a direct store is 32 two-byte
+// stores per lane. The values go through the wave's own [32][64] bf16 LDS
+// image instead (`stage`, STAGE_BYTES, touched by no other wave: no block
+// barrier) and leave as whole 128-byte rows: 8 lanes x 16 bytes per row, 4
+// store instructions. Same f2bf(acc * mul) values, same bytes in memory.
+// Banks: a ds_write_b16 group is one half-wave = 64 contiguous bytes of one
+// row; a ds_read_b128 group of 16 lanes covers four 64-byte half rows whose
+// offsets mod 256 are all different. Neither needs padding or a swizzle.
+constexpr int STAGE_BYTES = 32 * D * 2;
+
+// Orders a wave's LDS writes before its own later LDS reads (and the other
+// way round) where the two go through differently typed pointers. The LDS
+// runs one wave's accesses in program order; this is for the compiler.
+DEV_INLINE void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 template <typename F>
 DEV_INLINE void store_ctiles(bf16* p, int st, const BlockCtx& c,
-                             const f32x16 (&acc)[2], F mul) {
+                             const f32x16 (&acc)[2], F mul, char* stage) {
+  bf16* img = reinterpret_cast<bf16*>(stage);
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      p[crow(r, c.h32) * st + dt * 32 + c.x32] = f2bf(acc[dt][r] * mul(r));
+      img[crow(r, c.h32) * D + dt * 32 + c.x32] = f2bf(acc[dt][r] * mul(r));
+  wave_lds_fence();
+  const int piece = c.lane & 7;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = 8 * i + (c.lane >> 3);
+    store8(p + row * st + piece * 8,
+           *reinterpret_cast<const short8v*>(stage + row * (D * 2) +
+                                             piece * 16));
+  }
+  wave_lds_fence();   // the image is free for this wave's next result
 }
 
 // ---------------------------------------------------------------------------
@@ -329,24 +424,25 @@ constexpr int fwd_min_blocks(int nw, bool drop) {
   return nw == 8 ? (drop ? 3 : 4) : 2;
 }
 
-template <int NW, bool DROP = false>
+// One Q block (c.tile) of the forward; the kernel below calls it once per
+// pass. Everything but `c` and the LDS is re-created per pass; the first
+// pipe.next() of a pass holds the barrier that ends the previous pass's reads.
+template <int NW, bool DROP>
 // DROP: fused attention dropout — the row sum l_run uses the UNMASKED
 // exponentials (normalization is the true softmax sum) while the PV
 // accumulation consumes masked/rescaled P.
-__launch_bounds__(NW * WAVE, fwd_min_blocks(NW, DROP))
-__global__ void attn_fwd_kernel(const bf16* __restrict__ q,
-                                const bf16* __restrict__ k,
-                                const bf16* __restrict__ v,
-                                bf16* __restrict__ o, float* __restrict__ lse,
-                                int T, int H, float scale, GStride sq,
-                                GStride so, Dropout drop) {
+DEV_INLINE void attn_fwd_tile(const BlockCtx& c, char* smem,
+                              const bf16* __restrict__ q,
+                              const bf16* __restrict__ k,
+                              const bf16* __restrict__ v,
+                              bf16* __restrict__ o, float* __restrict__ lse,
+                              int T, int H, float scale, const GStride& sq,
+                              const GStride& so, const Dropout& drop) {
   constexpr int BM = NW * 32;
   constexpr int NT = NW * WAVE;
-  __shared__ __attribute__((aligned(16))) char smem[2 * KVB * D * 2];
   char* lds_k = smem;                 // [64][64] keys row-major
   char* lds_v = smem + KVB * D * 2;   // [64][64] values row-major
 
-  const BlockCtx c;                   // c.tile: Q block
   const long long boff = c.base(sq, H);
   const bf16* qp = q + boff + (long long)(c.tile * BM) * sq.t;
 
@@ -465,43 +561,67 @@ __global__ void attn_fwd_kernel(const bf16* __restrict__ q,
     __builtin_amdgcn_s_setprio(0);
   }
 
+  const BlockCtx e = c.fresh_lane();
   float linv_row[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r)
-    linv_row[r] = fast_rcp(__shfl(l_run, crow(r, c.h32), WAVE));
-  store_ctiles(o + c.base(so, H) + (long long)row_lo * so.t, so.t, c, o_acc,
-               [&](int r) { return linv_row[r]; });
-  if (c.lane < 32) {
-    lse[c.bh * T + row_me] = (m_run + log2f(l_run)) * LN2;
+    linv_row[r] = fast_rcp(__shfl(l_run, crow(r, e.h32), WAVE));
+  const int erow_lo = e.tile * BM + e.w * 32;
+  store_ctiles(o + e.base(so, H) + (long long)erow_lo * so.t, so.t, e, o_acc,
+               [&](int r) { return linv_row[r]; },
+               smem + 2 * KVB * D * 2 + e.w * STAGE_BYTES);
+  if (e.lane < 32) {
+    lse[e.bh * T + erow_lo + e.x32] = (m_run + log2f(l_run)) * LN2;
   }
+}
+
+// LDS of the forward and dq kernels: the K and V tiles, then one staging
+// image per wave for the epilogue.
+constexpr int attn_lds_bytes(int nw) {
+  return 2 * KVB * D * 2 + nw * STAGE_BYTES;
+}
+
+template <int NW, bool DROP = false>
+__launch_bounds__(NW * WAVE, fwd_min_blocks(NW, DROP))
+__global__ void attn_fwd_kernel(const bf16* __restrict__ q,
+                                const bf16* __restrict__ k,
+                                const bf16* __restrict__ v,
+                                bf16* __restrict__ o, float* __restrict__ lse,
+                                int T, int H, float scale, GStride sq,
+                                GStride so, Dropout drop, int balance) {
+  __shared__ __attribute__((aligned(16))) char smem[attn_lds_bytes(NW)];
+  BlockCtx c(T / (NW * 32), balance, true);
+  do {
+    attn_fwd_tile<NW, DROP>(c, smem, q, k, v, o, lse, T, H, scale, sq, so,
+                            drop);
+  } while (c.next_pass());
 }
 
 // ---------------------------------------------------------------------------
 // Backward dK/dV: one workgroup per (NW*32)-key block; wave w owns 32 keys.
 // ---------------------------------------------------------------------------
-template <int NW, bool DROP = false>
-// unconstrained VGPRs: the compiler takes ~256 (2 waves/SIMD) — capping to
-// 128 (MINW 4) spills 800 B/lane and 170 (MINW 3) still 288 B/lane, and the
-// measured time at 256 equals the kernel's best (169.8 us at B8)
-__launch_bounds__(NW * WAVE)
-__global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
-                                    const bf16* __restrict__ k,
-                                    const bf16* __restrict__ v,
-                                    const bf16* __restrict__ dout,
-                                    const float* __restrict__ lse,
-                                    const float* __restrict__ delta,
-                                    bf16* __restrict__ dk, bf16* __restrict__ dv,
-                                    int T, int H, float scale, GStride sq,
-                                    GStride so, GStride sd, Dropout drop) {
+// One key block (c.tile, c.x32: key in wave) of dK/dV, called once per pass.
+template <int NW, bool DROP>
+DEV_INLINE void attn_bwd_dkv_tile(const BlockCtx& c, char* smem,
+                                  const bf16* __restrict__ q,
+                                  const bf16* __restrict__ k,
+                                  const bf16* __restrict__ v,
+                                  const bf16* __restrict__ dout,
+                                  const float* __restrict__ lse,
+                                  const float* __restrict__ delta,
+                                  bf16* __restrict__ dk, bf16* __restrict__ dv,
+                                  int T, int H, float scale, const GStride& sq,
+                                  const GStride& so, const GStride& sd,
+                                  const Dropout& drop) {
   constexpr int BK = NW * 32;
   constexpr int NT = NW * WAVE;
-  __shared__ __attribute__((aligned(16))) char smem[2 * KVB * D * 2 + 2 * KVB * 4];
   char* lds_q = smem;
   char* lds_do = smem + KVB * D * 2;
-  float* lds_lse = reinterpret_cast<float*>(smem + 2 * KVB * D * 2);
+  char* stage = smem + 2 * KVB * D * 2 + c.w * STAGE_BYTES;
+  float* lds_lse =
+      reinterpret_cast<float*>(smem + 2 * KVB * D * 2 + NW * STAGE_BYTES);
   float* lds_dlt = lds_lse + KVB;
 
-  const BlockCtx c;                   // c.tile: key block, c.x32: key in wave
   const long long boff = c.base(sq, H);
   const int i0 = c.tile * BK / KVB;   // first Q tile that sees these keys
 
@@ -621,42 +741,61 @@ __global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
     __builtin_amdgcn_s_setprio(0);
   }
 
-  // dk and dv stores interleaved (not two store_ctiles passes): the order
-  // the epilogue was measured with
+  // dk, then dv, through the same staging image
   const long long doff = c.base(sd, H) + (long long)(key_lo) * sd.t;
   bf16* dkp = dk + doff;
   bf16* dvp = dv + doff;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      dkp[crow(r, c.h32) * sd.t + dt * 32 + c.x32] = f2bf(dk_acc[dt][r] * scale);
-      dvp[crow(r, c.h32) * sd.t + dt * 32 + c.x32] = f2bf(dv_acc[dt][r]);
-    }
+  store_ctiles(dkp, sd.t, c, dk_acc, [&](int) { return scale; }, stage);
+  store_ctiles(dvp, sd.t, c, dv_acc, [&](int) { return 1.0f; }, stage);
+}
+
+template <int NW, bool DROP = false>
+// unconstrained VGPRs: the compiler takes ~256 (2 waves/SIMD) — capping to
+// 128 (MINW 4) spills 800 B/lane and 170 (MINW 3) still 288 B/lane, and the
+// measured time at 256 equals the kernel's best (169.8 us at B8)
+__launch_bounds__(NW * WAVE)
+__global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
+                                    const bf16* __restrict__ k,
+                                    const bf16* __restrict__ v,
+                                    const bf16* __restrict__ dout,
+                                    const float* __restrict__ lse,
+                                    const float* __restrict__ delta,
+                                    bf16* __restrict__ dk, bf16* __restrict__ dv,
+                                    int T, int H, float scale, GStride sq,
+                                    GStride so, GStride sd, Dropout drop,
+                                    int balance) {
+  __shared__ __attribute__((aligned(16)))
+  char smem[attn_lds_bytes(NW) + 2 * KVB * 4];   // + lse and delta of a tile
+  BlockCtx c(T / (NW * 32), balance, false);
+  do {
+    attn_bwd_dkv_tile<NW, DROP>(c, smem, q, k, v, dout, lse, delta, dk, dv, T,
+                                H, scale, sq, so, sd, drop);
+  } while (c.next_pass());
 }
 
 // ---------------------------------------------------------------------------
 // Backward dQ: one workgroup per (NW*32)-row Q block; wave w owns 32 rows.
 // ---------------------------------------------------------------------------
-template <int NW, bool DROP = false>
-__launch_bounds__(NW * WAVE)  // capping at 128 VGPR spills 164 B/lane here
-__global__ void attn_bwd_dq_kernel(const bf16* __restrict__ q,
-                                   const bf16* __restrict__ k,
-                                   const bf16* __restrict__ v,
-                                   const bf16* __restrict__ o,
-                                   const bf16* __restrict__ dout,
-                                   const float* __restrict__ lse,
-                                   float* __restrict__ delta,
-                                   bf16* __restrict__ dq, int T, int H,
-                                   float scale, GStride sq, GStride so,
-                                   GStride sd, Dropout drop) {
+// One Q block (c.tile) of dQ, called once per pass.
+template <int NW, bool DROP>
+DEV_INLINE void attn_bwd_dq_tile(const BlockCtx& c, char* smem,
+                                 const bf16* __restrict__ q,
+                                 const bf16* __restrict__ k,
+                                 const bf16* __restrict__ v,
+                                 const bf16* __restrict__ o,
+                                 const bf16* __restrict__ dout,
+                                 const float* __restrict__ lse,
+                                 float* __restrict__ delta,
+                                 bf16* __restrict__ dq, int T, int H,
+                                 float scale, const GStride& sq,
+                                 const GStride& so, const GStride& sd,
+                                 const Dropout& drop) {
   constexpr int BM = NW * 32;
   constexpr int NT = NW * WAVE;
-  __shared__ __attribute__((aligned(16))) char smem[2 * KVB * D * 2];
   char* lds_k = smem;                     // K row-major
   char* lds_v = smem + KVB * D * 2;       // V row-major
+  char* stage = smem + 2 * KVB * D * 2 + c.w * STAGE_BYTES;
 
-  const BlockCtx c;                       // c.tile: Q block
   const long long boff = c.base(sq, H);
   const long long ooff = c.base(so, H) + (long long)(c.tile * BM) * so.t;
   const bf16* qp = q + boff + (long long)(c.tile * BM) * sq.t;
@@ -771,7 +910,27 @@ __global__ void attn_bwd_dq_kernel(const bf16* __restrict__ q,
   }
 
   store_ctiles(dq + c.base(sd, H) + (long long)row_lo * sd.t, sd.t, c, dq_acc,
-               [&](int) { return scale; });
+               [&](int) { return scale; }, stage);
+}
+
+template <int NW, bool DROP = false>
+__launch_bounds__(NW * WAVE)  // capping at 128 VGPR spills 164 B/lane here
+__global__ void attn_bwd_dq_kernel(const bf16* __restrict__ q,
+                                   const bf16* __restrict__ k,
+                                   const bf16* __restrict__ v,
+                                   const bf16* __restrict__ o,
+                                   const bf16* __restrict__ dout,
+                                   const float* __restrict__ lse,
+                                   float* __restrict__ delta,
+                                   bf16* __restrict__ dq, int T, int H,
+                                   float scale, GStride sq, GStride so,
+                                   GStride sd, Dropout drop, int balance) {
+  __shared__ __attribute__((aligned(16))) char smem[attn_lds_bytes(NW)];
+  BlockCtx c(T / (NW * 32), balance, true);
+  do {
+    attn_bwd_dq_tile<NW, DROP>(c, smem, q, k, v, o, dout, lse, delta, dq, T, H,
+                               scale, sq, so, sd, drop);
+  } while (c.next_pass());
 }
 
 // ---------------------------------------------------------------------------
@@ -807,6 +966,54 @@ static void attn_dispatch(int T, const char* nw_env, bool drop, F f) {
   if (drop) with_nw(std::true_type{}); else with_nw(std::false_type{});
 }
 
+// Workgroups of `Kernel` that the device holds at once (CUs x resident
+// blocks per CU, as the runtime computes it from the kernel's registers and
+// LDS); asked once per kernel.
+template <auto Kernel>
+static long long resident_blocks(int threads) {
+  static const long long n = [&]() -> long long {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                              dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kernel, threads,
+                                                     0) != hipSuccess) {
+      (void)hipGetLastError();
+      return 0;
+    }
+    return (long long)cus * per_cu;
+  }();
+  return n;
+}
+
+// The tile mapping and the grid of one launch. TDSA_ATTN_BALANCE, read at
+// every launch:
+//   0  one tile per workgroup, in windows of 8 heads (the mapping up to here)
+//   1  (default) tile pairs where the halved grid still fills every resident
+//      slot of the device, otherwise 2
+//   2  one tile per workgroup, the heaviest tiles of the whole grid first
+//  -1  tile pairs whatever the grid (small grids in tests)
+// Measured at H=16, T=1024 (profiles/attn_balance.txt): at B=32 pairs take
+// the forward from 161 to 129 us and the backward from 536 to 381 us, 2 is
+// level in the forward and 2 % behind in the backward; at B=8 the forward's
+// 256 pairs would fill half of its 512 slots, and 2 takes it from 47 to 38 us.
+struct TileMap {
+  int balance;
+  dim3 grid;
+};
+
+template <auto Kernel>
+static TileMap tile_map(int n_tiles, long long bh, int threads) {
+  int balance = (int)env_int("TDSA_ATTN_BALANCE", BAL_PAIRS);
+  const bool forced = balance == -1;
+  if (balance < BAL_OFF || balance > BAL_HEAVY) balance = BAL_PAIRS;
+  const int n_pairs = (n_tiles + 1) / 2;
+  if (balance == BAL_PAIRS && !forced &&
+      n_pairs * bh < resident_blocks<Kernel>(threads))
+    balance = BAL_HEAVY;
+  return {balance, dim3(balance == BAL_PAIRS ? n_pairs : n_tiles, bh)};
+}
+
 }  // namespace tdsa
 
 using namespace tdsa;
@@ -827,10 +1034,12 @@ hipError_t tdsa_attn_fwd(const void* q, const void* k, const void* v, void* o,
   const Dropout drop = make_dropout(dropout_p, seed);
   attn_dispatch(T, "TDSA_ATTN_FWD_NW", dropout_p > 0.0f, [&](auto nw, auto dr) {
     constexpr int NW = decltype(nw)::value;
-    hipLaunchKernelGGL((attn_fwd_kernel<NW, decltype(dr)::value>),
-                       dim3(T / (NW * 32), B * H), dim3(NW * WAVE), 0, stream,
+    constexpr auto fwd = attn_fwd_kernel<NW, decltype(dr)::value>;
+    const TileMap m = tile_map<fwd>(T / (NW * 32), B * H, NW * WAVE);
+    hipLaunchKernelGGL(fwd, m.grid, dim3(NW * WAVE), 0, stream,
                        (const bf16*)q, (const bf16*)k, (const bf16*)v,
-                       (bf16*)o, lse, T, (int)H, scale, sq, so, drop);
+                       (bf16*)o, lse, T, (int)H, scale, sq, so, drop,
+                       m.balance);
   });
   return hipGetLastError();
 }
@@ -850,15 +1059,21 @@ hipError_t tdsa_attn_bwd(const void* q, const void* k, const void* v,
   attn_dispatch(T, "TDSA_ATTN_BWD_NW", dropout_p > 0.0f, [&](auto nw, auto dr) {
     constexpr int NW = decltype(nw)::value;
     constexpr bool DROP = decltype(dr)::value;
-    const dim3 grid(T / (NW * 32), B * H), block(NW * WAVE);
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<NW, DROP>), grid, block, 0, stream,
+    constexpr auto dq_k = attn_bwd_dq_kernel<NW, DROP>;
+    constexpr auto dkv_k = attn_bwd_dkv_kernel<NW, DROP>;
+    const dim3 block(NW * WAVE);
+    // the two kernels differ in residency, so each gets its own mapping
+    const TileMap mq = tile_map<dq_k>(T / (NW * 32), B * H, NW * WAVE);
+    const TileMap mkv = tile_map<dkv_k>(T / (NW * 32), B * H, NW * WAVE);
+    hipLaunchKernelGGL(dq_k, mq.grid, block, 0, stream,
                        (const bf16*)q, (const bf16*)k, (const bf16*)v,
                        (const bf16*)o, (const bf16*)dout, lse, delta,
-                       (bf16*)dq, T, (int)H, scale, sq, so, sd, drop);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<NW, DROP>), grid, block, 0, stream,
+                       (bf16*)dq, T, (int)H, scale, sq, so, sd, drop,
+                       mq.balance);
+    hipLaunchKernelGGL(dkv_k, mkv.grid, block, 0, stream,
                        (const bf16*)q, (const bf16*)k, (const bf16*)v,
                        (const bf16*)dout, lse, delta, (bf16*)dk, (bf16*)dv, T,
-                       (int)H, scale, sq, so, sd, drop);
+                       (int)H, scale, sq, so, sd, drop, mkv.balance);
   });
   return hipGetLastError();
 }
