@@ -366,6 +366,22 @@ void launch_optim_multi(const char* what, const std::vector<Desc>& descs,
             what);
 }
 
+// The optional gradient scale of an update launch: one fp32 number on the
+// parameters' device, read by the kernel (no host copy). nullptr when absent.
+const float* grad_scale_ptr(const char* what,
+                            const c10::optional<at::Tensor>& grad_scale,
+                            const at::Device& device) {
+  if (!grad_scale.has_value()) return nullptr;
+  const at::Tensor& s = *grad_scale;
+  TORCH_CHECK(s.scalar_type() == at::kFloat, what,
+              ": grad_scale must be float32, got ", s.scalar_type());
+  TORCH_CHECK(s.numel() == 1, what, ": grad_scale has ", s.numel(),
+              " elements, expected 1");
+  TORCH_CHECK(s.device() == device, what, ": grad_scale is on ", s.device(),
+              ", the parameters on ", device);
+  return s.data_ptr<float>();
+}
+
 // One fused launch for a whole parameter list. vmaxs: all present (amsgrad)
 // or all absent.
 void adamw_step_multi(std::vector<at::Tensor> params,
@@ -374,13 +390,14 @@ void adamw_step_multi(std::vector<at::Tensor> params,
                       std::vector<c10::optional<at::Tensor>> masters,
                       std::vector<c10::optional<at::Tensor>> vmaxs,
                       double lr, double b1, double b2, double eps, double wd,
-                      int64_t step) {
+                      int64_t step, c10::optional<at::Tensor> grad_scale) {
   const char* what = "adamw_step_multi";
   const size_t n = params.size();
   TORCH_CHECK(grads.size() == n && ms.size() == n && vs.size() == n &&
               masters.size() == n && vmaxs.size() == n,
               what, ": length mismatch");
   if (n == 0) return;
+  const float* gscale = grad_scale_ptr(what, grad_scale, params[0].device());
   const bool amsgrad = vmaxs[0].has_value();
   std::vector<tdsa::AdamTensorDesc> descs(n);
   for (size_t i = 0; i < n; ++i) {
@@ -397,7 +414,7 @@ void adamw_step_multi(std::vector<at::Tensor> params,
                      [&](const void* blob, int ndescs, int nchunks) {
     return tdsa_adamw_multi(blob, ndescs, nchunks, amsgrad, (float)lr,
                             (float)b1, (float)b2, (float)eps, (float)wd, step,
-                            cur_stream());
+                            gscale, cur_stream());
   });
 }
 
@@ -408,12 +425,13 @@ void sgd_step_multi(std::vector<at::Tensor> params,
                     std::vector<c10::optional<at::Tensor>> masters,
                     std::vector<bool> first, double lr, double momentum,
                     double dampening, double wd, bool nesterov,
-                    bool maximize) {
+                    bool maximize, c10::optional<at::Tensor> grad_scale) {
   const char* what = "sgd_step_multi";
   const size_t n = params.size();
   TORCH_CHECK(grads.size() == n && bufs.size() == n && masters.size() == n &&
               first.size() == n, what, ": length mismatch");
   if (n == 0) return;
+  const float* gscale = grad_scale_ptr(what, grad_scale, params[0].device());
   std::vector<tdsa::SgdTensorDesc> descs(n);
   for (size_t i = 0; i < n; ++i) {
     auto& d = descs[i];
@@ -426,8 +444,38 @@ void sgd_step_multi(std::vector<at::Tensor> params,
                      [&](const void* blob, int ndescs, int nchunks) {
     return tdsa_sgd_multi(blob, ndescs, nchunks, (float)lr, (float)momentum,
                           (float)dampening, (float)wd, nesterov, maximize,
-                          cur_stream());
+                          gscale, cur_stream());
   });
+}
+
+// fp32 sum of squares of every gradient (bf16 and fp32 mixed) as a 0-dim
+// tensor on their device: the second user of the optimizer launch's blob.
+at::Tensor grad_sumsq_multi(std::vector<at::Tensor> grads) {
+  const char* what = "grad_sumsq_multi";
+  const size_t n = grads.size();
+  TORCH_CHECK(n > 0, what, ": empty gradient list");
+  std::vector<tdsa::GradNormDesc> descs(n);
+  long long nchunks = 0;
+  for (size_t i = 0; i < n; ++i) {
+    auto& d = descs[i];
+    TORCH_CHECK(grads[i].device() == grads[0].device(), what, ": grad[", i,
+                "] is on ", grads[i].device(), ", grad[0] on ",
+                grads[0].device());
+    d.numel = grads[i].numel();
+    d.g = entry_ptr(what, i, "grad", grads[i], d.numel, false);
+    d.bf16 = dtype_flag(grads[i]);
+    nchunks += (d.numel + tdsa::kOptimChunkElems - 1) / tdsa::kOptimChunkElems;
+  }
+  auto f32 = grads[0].options().dtype(at::kFloat);
+  auto partials = at::empty({nchunks}, f32);
+  auto out = at::empty({}, f32);
+  launch_optim_multi(what, descs, grads[0].device(),
+                     [&](const void* blob, int ndescs, int nch) {
+    return tdsa_grad_sumsq_multi(blob, ndescs, nch,
+                                 partials.data_ptr<float>(),
+                                 out.data_ptr<float>(), cur_stream());
+  });
+  return out;
 }
 
 // ---- TN GEMM (linear dW autotuner candidate) ------------------------------
@@ -592,8 +640,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("n_valid"), py::arg("ignore_index"),
           py::arg("out") = py::none());
   mod.def("gemm_tn", &gemm_tn);
-  mod.def("adamw_step_multi", &adamw_step_multi);
-  mod.def("sgd_step_multi", &sgd_step_multi);
+  mod.def("adamw_step_multi", &adamw_step_multi, py::arg("params"),
+          py::arg("grads"), py::arg("ms"), py::arg("vs"), py::arg("masters"),
+          py::arg("vmaxs"), py::arg("lr"), py::arg("b1"), py::arg("b2"),
+          py::arg("eps"), py::arg("wd"), py::arg("step"),
+          py::arg("grad_scale") = py::none());
+  mod.def("sgd_step_multi", &sgd_step_multi, py::arg("params"),
+          py::arg("grads"), py::arg("bufs"), py::arg("masters"),
+          py::arg("first"), py::arg("lr"), py::arg("momentum"),
+          py::arg("dampening"), py::arg("wd"), py::arg("nesterov"),
+          py::arg("maximize"), py::arg("grad_scale") = py::none());
+  mod.def("grad_sumsq_multi", &grad_sumsq_multi, py::arg("grads"));
   mod.def("attention_fwd", &attention_fwd, py::arg("q"), py::arg("k"),
           py::arg("v"), py::arg("scale"), py::arg("out") = py::none(),
           py::arg("dropout_p") = 0.0, py::arg("seed") = 0);

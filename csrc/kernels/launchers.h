@@ -86,14 +86,25 @@ hipError_t tdsa_ce_bwd(const void* logits, const long long* targets,
 // ---- optim.hip --------------------------------------------------------------
 // blob: ndescs tensor descriptors followed by nchunks ChunkRef entries
 // (optim_desc.h), on the device. amsgrad: every descriptor carries a vmax.
-// step: the global 1-based optimizer step.
+// step: the global 1-based optimizer step. gscale: one fp32 number on the
+// device that every gradient element is multiplied by before the update
+// (the clip coefficient); nullptr: the gradients are used as they are.
 hipError_t tdsa_adamw_multi(const void* blob, int ndescs, int nchunks,
                             int amsgrad, float lr, float b1, float b2,
                             float eps, float wd, long long step,
-                            hipStream_t stream);
+                            const float* gscale, hipStream_t stream);
 hipError_t tdsa_sgd_multi(const void* blob, int ndescs, int nchunks, float lr,
                           float momentum, float dampening, float wd,
-                          int nesterov, int maximize, hipStream_t stream);
+                          int nesterov, int maximize, const float* gscale,
+                          hipStream_t stream);
+
+// ---- gradnorm.hip -----------------------------------------------------------
+// Sum of squares of every gradient of the blob ([GradNormDesc][ChunkRef]) as
+// one fp32 number at `out`. partials: nchunks floats of scratch. nchunks may
+// be 0 (every tensor empty): out = 0.
+hipError_t tdsa_grad_sumsq_multi(const void* blob, int ndescs, int nchunks,
+                                 float* partials, float* out,
+                                 hipStream_t stream);
 
 // ---- attention.hip ----------------------------------------------------------
 // bf16 (B, H, T, 64) tensors with T % 64 == 0 and a contiguous last dim.

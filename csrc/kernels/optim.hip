@@ -19,10 +19,21 @@ namespace tdsa {
 // the element-wise form compiled to scalar flat_load_dword (checked in the
 // .s — the unroll never re-vectorized). HASM as a template so the master
 // loads/stores are unconditional in the fast path.
-template <int S, bool HASM, typename Rule, typename PT, typename GT>
+//
+// HASG: every gradient element is multiplied by `gs` (the clip coefficient of
+// a max_grad_norm step) in fp32 before the rule sees it. A template flag and
+// not a multiply by 1.0f, so that the unscaled instantiations keep the
+// instruction stream they had before the scale existed.
+template <bool HASG>
+DEV_INLINE float scaled(float g, float gs) {
+#pragma clang fp contract(off)
+  return HASG ? g * gs : g;
+}
+
+template <int S, bool HASM, bool HASG, typename Rule, typename PT, typename GT>
 DEV_INLINE void update_span(const Rule& rule, PT* p, const GT* g,
                             const typename Rule::Desc& d, float* const* st,
-                            long long start, long long end) {
+                            long long start, long long end, float gs) {
   // params/grads 4 wide in either dtype, next to the fp32 state vectors
   typedef Vec<PT, 4> PVec;
   typedef Vec<GT, 4> GVec;
@@ -51,7 +62,8 @@ DEV_INLINE void update_span(const Rule& rule, PT* p, const GT* g,
       float s[S + 1];
 #pragma unroll
       for (int j = 0; j < S; ++j) s[j] = sv[j][k];
-      pv[k] = rule.template elem<S>(d, GVec::get(gv, k), pv[k], s);
+      pv[k] = rule.template elem<S>(d, scaled<HASG>(GVec::get(gv, k), gs),
+                                    pv[k], s);
 #pragma unroll
       for (int j = 0; j < S; ++j) sv[j][k] = s[j];
       PVec::set(pout, k, pv[k]);
@@ -66,7 +78,7 @@ DEV_INLINE void update_span(const Rule& rule, PT* p, const GT* g,
 #pragma unroll
     for (int j = 0; j < S; ++j) s[j] = st[j][i];
     const float pk = rule.template elem<S>(
-        d, (float)g[i], HASM ? master[i] : (float)p[i], s);
+        d, scaled<HASG>((float)g[i], gs), HASM ? master[i] : (float)p[i], s);
 #pragma unroll
     for (int j = 0; j < S; ++j) st[j][i] = s[j];
     if (HASM) master[i] = pk;
@@ -99,15 +111,15 @@ struct AdamW {
     return fmaf(p, fmaf(-lr, wd, 1.0f), -step);
   }
 
-  template <typename PT, typename GT>
+  template <bool HASG, typename PT, typename GT>
   DEV_INLINE void chunk(PT* p, const GT* g, const Desc& d, long long start,
-                        long long end) const {
+                        long long end, float gs) const {
     constexpr int S = AMS ? 3 : 2;
     float* const st[3] = {d.m, d.v, d.vmax};
     if (d.master)
-      update_span<S, true>(*this, p, g, d, st, start, end);
+      update_span<S, true, HASG>(*this, p, g, d, st, start, end, gs);
     else
-      update_span<S, false>(*this, p, g, d, st, start, end);
+      update_span<S, false, HASG>(*this, p, g, d, st, start, end, gs);
   }
 };
 
@@ -130,53 +142,66 @@ struct Sgd {
     return fmaf(-lr, g, p);
   }
 
-  template <typename PT, typename GT>
+  template <bool HASG, typename PT, typename GT>
   DEV_INLINE void chunk(PT* p, const GT* g, const Desc& d, long long start,
-                        long long end) const {
+                        long long end, float gs) const {
     float* const st[1] = {d.buf};
     if (d.buf && d.master)
-      update_span<1, true>(*this, p, g, d, st, start, end);
+      update_span<1, true, HASG>(*this, p, g, d, st, start, end, gs);
     else if (d.buf)
-      update_span<1, false>(*this, p, g, d, st, start, end);
+      update_span<1, false, HASG>(*this, p, g, d, st, start, end, gs);
     else if (d.master)
-      update_span<0, true>(*this, p, g, d, st, start, end);
+      update_span<0, true, HASG>(*this, p, g, d, st, start, end, gs);
     else
-      update_span<0, false>(*this, p, g, d, st, start, end);
+      update_span<0, false, HASG>(*this, p, g, d, st, start, end, gs);
   }
 };
 
 // The chunk loop and the (param, grad) dtype ladder of both optimizers.
-template <typename Rule>
+// HASG: gscale points at the gradient scale, which each lane reads once,
+// before its chunk loop; without it gscale is not touched.
+template <typename Rule, bool HASG>
 __global__ void optim_multi_kernel(
     const typename Rule::Desc* __restrict__ descs,
     const ChunkRef* __restrict__ chunks, int nchunks, int chunk_elems,
-    Rule rule) {
+    Rule rule, const float* __restrict__ gscale) {
+  const float gs = HASG ? *gscale : 1.0f;
   for (int cid = blockIdx.x; cid < nchunks; cid += gridDim.x) {
     const ChunkRef ch = chunks[cid];
     const typename Rule::Desc d = descs[ch.tensor];
     const long long start = (long long)ch.chunk * chunk_elems;
     const long long end = min(d.numel, start + chunk_elems);
     if (d.param_bf16 && d.grad_bf16)
-      rule.chunk((bf16*)d.p, (const bf16*)d.g, d, start, end);
+      rule.template chunk<HASG>((bf16*)d.p, (const bf16*)d.g, d, start, end,
+                                gs);
     else if (d.param_bf16)
-      rule.chunk((bf16*)d.p, (const float*)d.g, d, start, end);
+      rule.template chunk<HASG>((bf16*)d.p, (const float*)d.g, d, start, end,
+                                gs);
     else if (d.grad_bf16)
-      rule.chunk((float*)d.p, (const bf16*)d.g, d, start, end);
+      rule.template chunk<HASG>((float*)d.p, (const bf16*)d.g, d, start, end,
+                                gs);
     else
-      rule.chunk((float*)d.p, (const float*)d.g, d, start, end);
+      rule.template chunk<HASG>((float*)d.p, (const float*)d.g, d, start, end,
+                                gs);
   }
 }
 
 // Grid sizing, blob split and launch.
 template <typename Rule>
 hipError_t launch_multi(const Rule& rule, const void* blob, int ndescs,
-                        int nchunks, hipStream_t stream) {
+                        int nchunks, const float* gscale, hipStream_t stream) {
   const typename Rule::Desc* descs = (const typename Rule::Desc*)blob;
   const ChunkRef* chunks = (const ChunkRef*)(descs + ndescs);
   int grid = nchunks < 2048 ? nchunks : 2048;
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(optim_multi_kernel<Rule>, dim3(grid), dim3(256), 0,
-                     stream, descs, chunks, nchunks, kOptimChunkElems, rule);
+  if (gscale)
+    hipLaunchKernelGGL((optim_multi_kernel<Rule, true>), dim3(grid), dim3(256),
+                       0, stream, descs, chunks, nchunks, kOptimChunkElems,
+                       rule, gscale);
+  else
+    hipLaunchKernelGGL((optim_multi_kernel<Rule, false>), dim3(grid),
+                       dim3(256), 0, stream, descs, chunks, nchunks,
+                       kOptimChunkElems, rule, gscale);
   return hipGetLastError();
 }
 
@@ -190,21 +215,22 @@ extern "C" {
 hipError_t tdsa_adamw_multi(const void* blob, int ndescs, int nchunks,
                             int amsgrad, float lr, float b1, float b2,
                             float eps, float wd, long long step,
-                            hipStream_t stream) {
+                            const float* gscale, hipStream_t stream) {
   const float inv_bc1 = 1.0f / (1.0f - powf(b1, (float)step));
   const float inv_bc2 = 1.0f / (1.0f - powf(b2, (float)step));
   if (amsgrad)
     return launch_multi(AdamW<true>{lr, b1, b2, eps, wd, inv_bc1, inv_bc2},
-                        blob, ndescs, nchunks, stream);
+                        blob, ndescs, nchunks, gscale, stream);
   return launch_multi(AdamW<false>{lr, b1, b2, eps, wd, inv_bc1, inv_bc2},
-                      blob, ndescs, nchunks, stream);
+                      blob, ndescs, nchunks, gscale, stream);
 }
 
 hipError_t tdsa_sgd_multi(const void* blob, int ndescs, int nchunks, float lr,
                           float momentum, float dampening, float wd,
-                          int nesterov, int maximize, hipStream_t stream) {
+                          int nesterov, int maximize, const float* gscale,
+                          hipStream_t stream) {
   return launch_multi(Sgd{lr, momentum, dampening, wd, nesterov, maximize},
-                      blob, ndescs, nchunks, stream);
+                      blob, ndescs, nchunks, gscale, stream);
 }
 
 }  // extern "C"

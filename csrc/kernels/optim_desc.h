@@ -1,6 +1,6 @@
 // Device-blob layout of the multi-tensor optimizer launches, shared by the
 // host code that fills it (bind.cpp) and the kernels that read it
-// (optim.hip). Plain C++: no HIP or torch types.
+// (optim.hip, gradnorm.hip). Plain C++: no HIP or torch types.
 //
 // blob = [ndescs x *TensorDesc][nchunks x ChunkRef], device memory. Each
 // workgroup takes one ChunkRef at a time: kOptimChunkElems elements of one
@@ -32,6 +32,13 @@ struct SgdTensorDesc {
   int param_bf16;
   int grad_bf16;
   int first;      // this tensor's first step: buf is set to the gradient
+};
+
+// One gradient of the sum-of-squares launch (gradnorm.hip).
+struct GradNormDesc {
+  const void* g;
+  long long numel;
+  int bf16;
 };
 
 struct ChunkRef {

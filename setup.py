@@ -21,6 +21,7 @@ SOURCES = [
     "csrc/kernels/embedding.hip",
     "csrc/kernels/cross_entropy.hip",
     "csrc/kernels/optim.hip",
+    "csrc/kernels/gradnorm.hip",
     "csrc/kernels/attention.hip",
     "csrc/kernels/gemm_tn.hip",
     "csrc/kernels/debug.hip",

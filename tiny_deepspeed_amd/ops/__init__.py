@@ -18,7 +18,7 @@ from .embedding import embedding_forward, embedding_weight_grad
 from .gelu import gelu, gelu_fwd, gelu_bwd
 from .attention import causal_attention, fused_causal_attention
 from .cross_entropy import cross_entropy, cross_entropy_fwd, cross_entropy_bwd
-from .optim_ops import adamw_step, sgd_step
+from .optim_ops import adamw_step, sgd_step, grad_sumsq, clip_coef
 from .autotuner import RuntimeAutoTuner, default_tuner
 from ._ext import ext_available, get_ext
 from .utils import acc_dtype
@@ -30,7 +30,7 @@ __all__ = [
     "gelu", "gelu_fwd", "gelu_bwd",
     "causal_attention", "fused_causal_attention",
     "cross_entropy", "cross_entropy_fwd", "cross_entropy_bwd",
-    "adamw_step", "sgd_step",
+    "adamw_step", "sgd_step", "grad_sumsq", "clip_coef",
     "RuntimeAutoTuner", "default_tuner",
     "ext_available", "get_ext",
     "acc_dtype",

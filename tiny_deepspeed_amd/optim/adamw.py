@@ -14,8 +14,8 @@ from .. import ops
 
 class AdamW(Optimizer):
     def __init__(self, parameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=1e-2, amsgrad=False):
-        super().__init__(parameters, lr)
+                 weight_decay=1e-2, amsgrad=False, max_grad_norm=None):
+        super().__init__(parameters, lr, max_grad_norm=max_grad_norm)
         if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError(f"Invalid betas: {betas}")
         if eps <= 0.0:
@@ -61,6 +61,7 @@ class AdamW(Optimizer):
         ops.get_ext().adamw_step_multi(
             params, grads, ms, vs, masters, vmaxs, self.lr, self.beta1,
             self.beta2, self.eps, self.weight_decay, self.t,
+            self._grad_scale,
         )
 
     @torch.no_grad()
@@ -70,6 +71,7 @@ class AdamW(Optimizer):
             self.master.get(name), self.t, self.lr, self.beta1, self.beta2,
             self.eps, self.weight_decay,
             max_exp_avg_sq=self.max_exp_avg_sq.get(name),
+            grad_scale=self._grad_scale,
         )
 
     def _state_tensors(self):

@@ -13,8 +13,9 @@ from .. import ops
 
 class SGD(Optimizer):
     def __init__(self, parameters, lr=1e-3, momentum=0.0, dampening=0.0,
-                 weight_decay=0.0, nesterov=False, maximize=False):
-        super().__init__(parameters, lr)
+                 weight_decay=0.0, nesterov=False, maximize=False,
+                 max_grad_norm=None):
+        super().__init__(parameters, lr, max_grad_norm=max_grad_norm)
         if momentum < 0.0:
             raise ValueError(f"Invalid momentum: {momentum}")
         if nesterov and (momentum <= 0.0 or dampening != 0.0):
@@ -56,6 +57,7 @@ class SGD(Optimizer):
         ops.get_ext().sgd_step_multi(
             params, grads, bufs, masters, first, self.lr, self.momentum,
             self.dampening, self.weight_decay, self.nesterov, self.maximize,
+            self._grad_scale,
         )
 
     @torch.no_grad()
@@ -66,6 +68,7 @@ class SGD(Optimizer):
             param.data, param.grad, self.velocities.get(name),
             self.master.get(name), self.lr, self.momentum, self.dampening,
             self.weight_decay, self.nesterov, self.maximize, first,
+            grad_scale=self._grad_scale,
         )
 
     def _state_tensors(self):

@@ -39,6 +39,13 @@ class _ZeroOptimMixin:
         # device-side wait for in-flight grad reduces
         self.comm.sync()
 
+    def _reduce_sumsq(self, sumsq):
+        # the items of a step are the OWNED gradients, so the ranks' sums are
+        # disjoint pieces of the global one. Every rank calls this every step
+        # (with 0.0 when it owns nothing or nothing got a gradient): a rank
+        # that stayed out of the collective would hang the others.
+        return self.comm.all_reduce_sum(sumsq)
+
     def post_step(self):
         if self.broadcast_params_after_step and not self.comm._inactive():
             # refresh replicas: bucketed async broadcasts from each owner,

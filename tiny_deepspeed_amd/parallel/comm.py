@@ -328,6 +328,17 @@ class CommContext:
         t.div_(self.world_size)
         return t
 
+    def all_reduce_sum(self, t):
+        """In-place sum of a small tensor (the squared gradient norm of a
+        clipped step) on the current stream: issued after pre_step()'s
+        sync(), so it orders behind the gradient reduces, and the update that
+        reads it is enqueued behind it; on GPU the host does not wait."""
+        if self._inactive():
+            return t
+        self._count("all_reduce", t)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.pg[REDUCE])
+        return t
+
 
 _DEFAULT = None
 

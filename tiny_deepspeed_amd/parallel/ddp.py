@@ -74,7 +74,10 @@ class DDP(ModelWrapper):
 
 class _DDPOptimMixin:
     """Local step; the only distributed action is waiting for in-flight
-    grad all-reduces (device-side) before the first update."""
+    grad all-reduces (device-side) before the first update. Clipping
+    (max_grad_norm) needs no collective either: after that wait every rank
+    holds the same averaged gradients, so the base _reduce_sumsq (identity)
+    gives every rank the same global norm."""
 
     def _setup_comm(self, comm):
         from .comm import default_comm

@@ -206,10 +206,17 @@ class _FlatOptimMixin:
         self.comm.sync()
         self.engine.reset_fired()
 
+    def _reduce_sumsq(self, sumsq):
+        # the grad shards of the ranks tile every bucket; the padding behind
+        # the last parameter is zero on every rank and adds nothing
+        return self.comm.all_reduce_sum(sumsq)
+
     @torch.no_grad()
     def _run_step(self):
         self.pre_step()
-        self._apply_updates(list(self.params.items()))
+        items = list(self.params.items())
+        self._clip(items)
+        self._apply_updates(items)
         self.post_step()
         # grads live in persistent bucket buffers; nothing to clear
 
