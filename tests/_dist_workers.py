@@ -187,7 +187,7 @@ def grad_accumulation(rank, world):
 
 def fused_lmhead_strategy_losses(rank, world, strategy):
     """Strategy training with fused_lm_head=True: dW publication must go
-    through publish_weight_grad into the strategy's collective."""
+    through the module's _publish hook into the strategy's collective."""
     import tiny_deepspeed_amd as tdsa
     from tiny_deepspeed_amd.models import GPTConfig, GPT2Model
 

@@ -87,7 +87,7 @@ def test_model_uses_fused_path_and_trains(monkeypatch):
 @pytest.mark.parametrize("strategy", ["ddp", "zero2", "zero3", "zero2flat"])
 def test_fused_lmhead_strategy_parity_world2(strategy):
     """dW of the fused path must flow through each strategy's collective
-    (publish_weight_grad): world-2 losses == single-device fused losses."""
+    (the _publish hook): world-2 losses == single-device fused losses."""
     from tests.dist_utils import run_distributed
     from tests import _dist_workers as w
 

@@ -1,4 +1,4 @@
-"""Module layer: autograd-owning nn modules with overridable callbacks.
+"""Module layer: autograd-owning nn modules; strategies override their hooks.
 
 Parity with ``/root/reference/tiny_deepspeed/core/module/`` (Linear,
 LayerNorm, Embedding). Conv is deliberately absent, matching the

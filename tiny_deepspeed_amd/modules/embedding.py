@@ -1,4 +1,4 @@
-"""Embedding module with overridable callbacks.
+"""Embedding module: callbacks over overridable hooks (see linear.py).
 
 Parity with ``/root/reference/tiny_deepspeed/core/module/embedding.py:15-98``
 (padding_idx plumbing; backward returns (None, grad_weight)). max_norm is
@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from .linear import _ParamHooks, _check_grad_shape
 
 
 class _EmbeddingFn(torch.autograd.Function):
@@ -17,7 +18,7 @@ class _EmbeddingFn(torch.autograd.Function):
     def forward(ctx, idx, weight, module):
         ctx.module = module
         ctx.save_for_backward(idx)
-        return module.forward_callback(idx, weight)
+        return module.forward_callback(idx)
 
     @staticmethod
     def backward(ctx, dy):
@@ -26,7 +27,7 @@ class _EmbeddingFn(torch.autograd.Function):
         return None, dw, None
 
 
-class Embedding(nn.Embedding):
+class Embedding(_ParamHooks, nn.Embedding):
     def __init__(self, num_embeddings, embedding_dim, padding_idx=None,
                  max_norm=None, norm_type=2.0, scale_grad_by_freq=False,
                  sparse=False, _weight=None, device=None, dtype=None,
@@ -39,8 +40,9 @@ class Embedding(nn.Embedding):
                          _weight=_weight, device=device, dtype=dtype)
         self.tuner = ops.RuntimeAutoTuner() if auto_tune else None
 
-    # --- overridable callbacks -------------------------------------------
-    def forward_callback(self, idx, weight):
+    # --- callbacks of _EmbeddingFn ---------------------------------------
+    def forward_callback(self, idx):
+        weight, _ = self._params_fwd()
         return ops.embedding_forward(weight, idx, padding_idx=self.padding_idx,
                                      tuner=self.tuner)
 
@@ -50,8 +52,8 @@ class Embedding(nn.Embedding):
         dw = ops.embedding_weight_grad(idx, dy, self.num_embeddings,
                                        padding_idx=self.padding_idx,
                                        tuner=self.tuner)
-        assert dw.shape == self.weight.shape
-        return dw
+        _check_grad_shape(self.weight, dw)
+        return self._publish(self.weight, dw)
 
     def forward(self, idx):
         return _EmbeddingFn.apply(idx, self.weight, self)

@@ -1,15 +1,15 @@
-"""Linear module with overridable forward/backward callbacks.
+"""Linear module: forward/backward callbacks over overridable hooks.
 
 Same load-bearing design as the reference's callback indirection
 (``/root/reference/tiny_deepspeed/core/module/linear.py:16-92``): forward
 and backward route through a torch.autograd.Function whose bodies are
-overridable instance methods, which is what lets the parallel strategies
-(parallel/ddp.py etc.) inject RCCL collectives between the dW computation
-and the dX computation for compute/comm overlap.
+instance methods, which is what lets the parallel strategies (parallel/)
+inject RCCL collectives between the dW computation and the dX computation
+for compute/comm overlap.
 
-Backward contract: `backward_callback(dy, x, weight)` returns
-(dx, dweight_or_None, dbias_or_None). The base class computes local grads
-with no communication.
+Backward contract: `backward_callback(dy, x)` returns (dx, dweight, dbias),
+each gradient being whatever `_publish` made of it. The callbacks are
+written once, here; a strategy changes only the three `_ParamHooks`.
 """
 
 import os
@@ -18,6 +18,31 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+
+
+class _ParamHooks:
+    """Where a module's callbacks get their parameters and what becomes of a
+    finished gradient: the two decisions a parallel strategy takes. The base
+    answers are the module's own parameters and plain autograd."""
+
+    def _params_fwd(self):
+        """(weight, bias) to compute the forward with."""
+        return self.weight, getattr(self, "bias", None)
+
+    def _weight_bwd(self):
+        """Weight for the input gradient; called first in backward."""
+        return self.weight
+
+    def _publish(self, param, grad):
+        """Dispose of param's finished gradient; autograd gets the result."""
+        return grad
+
+
+def _check_grad_shape(param, grad):
+    # a ZeRO-3 non-owner's storage is empty: compare with the full shape
+    full = getattr(param, "_tdsa_full_shape", param.shape)
+    assert tuple(grad.shape) == tuple(full), (
+        f"grad shape {tuple(grad.shape)} != parameter {tuple(full)}")
 
 
 def _ce_chunk_rows(V):
@@ -44,19 +69,17 @@ class _LinearCEFn(torch.autograd.Function):
     LLC-resident) and backward RECOMPUTES each chunk's logits from (x, lse),
     so only the per-row logsumexp (4 bytes/row) survives the forward.
 
-    Weight handling goes through three overridable module hooks so every
-    parallel strategy keeps its semantics (same callback-factory design as
-    _LinearFn): ``_ce_weight_fwd``/``_ce_weight_bwd`` provide the (possibly
-    JIT-gathered, ZeRO-3) full weight; ``publish_weight_grad`` routes dW
-    into the strategy's collective (DDP all-reduce / ZeRO reduce-to-owner)
-    and returns None, or returns dW for plain autograd accumulation.
+    Weight handling goes through the module's ``_ParamHooks``, as in
+    _LinearFn's callbacks, so every parallel strategy keeps its semantics:
+    the (possibly JIT-gathered, ZeRO-3) full weight in both directions, and
+    dW routed into the strategy's collective or handed back to autograd.
     """
 
     @staticmethod
     def forward(ctx, x, weight, targets, module, ignore_index):
         x2 = x.reshape(-1, x.shape[-1])
         tg = targets.reshape(-1)
-        w = module._ce_weight_fwd()
+        w, _ = module._params_fwd()
         R = x2.shape[0]
         V = w.shape[0]
         C = _ce_chunk_rows(V)
@@ -82,7 +105,7 @@ class _LinearCEFn(torch.autograd.Function):
     def backward(ctx, dloss):
         x2, tg, lse, n_valid = ctx.saved_tensors
         module = ctx.module
-        w = module._ce_weight_bwd()
+        w = module._weight_bwd()
         R, E = x2.shape
         V = w.shape[0]
         C = _ce_chunk_rows(V)
@@ -99,8 +122,8 @@ class _LinearCEFn(torch.autograd.Function):
                 dloss, logits_c, tg[s:e], lse[s:e], nv, ctx.ignore_index,
                 tuner=module.tuner, out=dlogits[s:e])
         dx2 = ops.linear_input_grad(dlogits, w)
-        dw = module.publish_weight_grad(
-            ops.linear_weight_grad(dlogits, x2))
+        dw = module._publish(module.weight,
+                             ops.linear_weight_grad(dlogits, x2))
         return dx2.view(ctx.x_shape), dw, None, None, None
 
 
@@ -108,9 +131,10 @@ class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, module):
         ctx.module = module
-        y = module.forward_callback(x, weight, bias)
+        # weight and bias are inputs for autograd's sake; the callback reads
+        # them through the module's hooks
+        y = module.forward_callback(x)
         ctx.save_for_backward(x)
-        ctx.has_bias = bias is not None
         return y
 
     @staticmethod
@@ -120,7 +144,7 @@ class _LinearFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
-class Linear(nn.Linear):
+class Linear(_ParamHooks, nn.Linear):
     """Drop-in nn.Linear whose fwd/bwd go through the op layer."""
 
     def __init__(self, in_features, out_features, bias=True, device=None,
@@ -128,39 +152,27 @@ class Linear(nn.Linear):
         super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)
         self.tuner = ops.RuntimeAutoTuner() if auto_tune else None
 
-    # --- overridable callbacks -------------------------------------------
-    def forward_callback(self, x, weight, bias):
+    # --- callbacks of _LinearFn ------------------------------------------
+    def forward_callback(self, x):
+        weight, bias = self._params_fwd()
         return ops.linear_forward(x, weight, bias, tuner=self.tuner)
 
     def backward_callback(self, dy, x):
-        dw = ops.linear_weight_grad(dy, x, tuner=self.tuner) if self.weight.requires_grad else None
-        db = (
-            ops.linear_bias_grad(dy, tuner=self.tuner)
-            if (self.bias is not None and self.bias.requires_grad)
-            else None
-        )
-        dx = ops.linear_input_grad(dy, self.weight, tuner=self.tuner)
-        self._assert_grad_shapes(dw, db)
+        # the order is what comm/compute overlap rests on: a strategy's
+        # _publish launches the gradient's collective, so dW and db are
+        # published as they appear and dX, last, runs underneath them
+        w = self._weight_bwd()
+        dw = db = None
+        if self.weight.requires_grad:
+            dw = ops.linear_weight_grad(dy, x, tuner=self.tuner)
+            _check_grad_shape(self.weight, dw)
+            dw = self._publish(self.weight, dw)
+        if self.bias is not None and self.bias.requires_grad:
+            db = ops.linear_bias_grad(dy, tuner=self.tuner)
+            _check_grad_shape(self.bias, db)
+            db = self._publish(self.bias, db)
+        dx = ops.linear_input_grad(dy, w, tuner=self.tuner)
         return dx, dw, db
-
-    def _assert_grad_shapes(self, dw, db):
-        if dw is not None:
-            assert dw.shape == self.weight.shape, (
-                f"dW shape {tuple(dw.shape)} != weight {tuple(self.weight.shape)}"
-            )
-        if db is not None and self.bias is not None:
-            assert db.shape == self.bias.shape
-
-    # --- fused projection + cross-entropy hooks (see _LinearCEFn) --------
-    def _ce_weight_fwd(self):
-        return self.weight
-
-    def _ce_weight_bwd(self):
-        return self.weight
-
-    def publish_weight_grad(self, dw):
-        """No strategy: hand dW back to autograd for plain accumulation."""
-        return dw
 
     def project_cross_entropy(self, x, targets, ignore_index=-100):
         """loss = cross_entropy(x @ W.T, targets), row-chunked so the full

@@ -1,4 +1,4 @@
-"""LayerNorm module with overridable callbacks.
+"""LayerNorm module: callbacks over overridable hooks (see linear.py).
 
 Parity with ``/root/reference/tiny_deepspeed/core/module/normalization.py:19-109``
 including its restrictions: elementwise affine with bias required, and only
@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from .linear import _ParamHooks, _check_grad_shape
 
 
 class _LayerNormResFn(torch.autograd.Function):
@@ -22,7 +23,7 @@ class _LayerNormResFn(torch.autograd.Function):
         # don't materialize an all-zeros dh when h is unused (ln_f discards
         # it) — backward treats dh=None as the plain no-fold path
         ctx.set_materialize_grads(False)
-        h, y, mean, rstd = module.forward_res_callback(x, res, weight, bias)
+        h, y, mean, rstd = module.forward_res_callback(x, res)
         ctx.save_for_backward(h, mean, rstd)
         return h, y
 
@@ -39,7 +40,7 @@ class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, module):
         ctx.module = module
-        y, mean, rstd = module.forward_callback(x, weight, bias)
+        y, mean, rstd = module.forward_callback(x)
         ctx.save_for_backward(x, mean, rstd)
         return y
 
@@ -50,7 +51,7 @@ class _LayerNormFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
-class LayerNorm(nn.LayerNorm):
+class LayerNorm(_ParamHooks, nn.LayerNorm):
     def __init__(self, normalized_shape, eps=1e-5, elementwise_affine=True,
                  bias=True, device=None, dtype=None, auto_tune=False):
         if not elementwise_affine or not bias:
@@ -68,29 +69,29 @@ class LayerNorm(nn.LayerNorm):
             )
         self.tuner = ops.RuntimeAutoTuner() if auto_tune else None
 
-    # --- overridable callbacks -------------------------------------------
-    def forward_callback(self, x, weight, bias):
+    # --- callbacks of the Functions above (parameters come through the
+    # module's hooks; the Functions take them for autograd's sake) ---------
+    def forward_callback(self, x):
+        weight, bias = self._params_fwd()
         return ops.layernorm_fwd(x, weight, bias, eps=self.eps, tuner=self.tuner)
 
-    def forward_res_callback(self, x, res, weight, bias):
+    def forward_res_callback(self, x, res):
+        weight, bias = self._params_fwd()
         return ops.layernorm_fwd_res(x, res, weight, bias, eps=self.eps,
                                      tuner=self.tuner)
 
     def backward_callback(self, dy, x, mean, rstd, dh=None):
-        dx, ws = ops.layernorm_dx(dy, x, self.weight, mean, rstd, dh=dh,
+        w = self._weight_bwd()
+        dx, ws = ops.layernorm_dx(dy, x, w, mean, rstd, dh=dh,
                                   tuner=self.tuner)
+        dw = db = None
         if self.weight.requires_grad:
             dw, db = ops.layernorm_dwdb(ws, dtype=self.weight.dtype, tuner=self.tuner)
-            self._assert_grad_shapes(dw, db)
-        else:
-            dw = db = None
+            _check_grad_shape(self.weight, dw)
+            _check_grad_shape(self.bias, db)
+            dw = self._publish(self.weight, dw)
+            db = self._publish(self.bias, db)
         return dx, dw, db
-
-    def _assert_grad_shapes(self, dw, db):
-        if dw is not None:
-            assert dw.shape == self.weight.shape
-        if db is not None:
-            assert db.shape == self.bias.shape
 
     def forward(self, x):
         return _LayerNormFn.apply(x, self.weight, self.bias, self)

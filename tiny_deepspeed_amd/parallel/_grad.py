@@ -11,6 +11,9 @@ just the last microbatch's contribution (the reference reduces only the
 current dW — SURVEY.md 2.9 note).
 """
 
+import torch.nn as nn
+
+from .. import modules as base
 from .wrapper import take_sync
 
 # publication modes
@@ -63,3 +66,26 @@ def publish_grad(comm, param, dw, mode):
                 param.grad = None
     else:
         raise ValueError(mode)
+
+
+class _PublishMixin:
+    """A strategy module's gradient hook: the base callbacks hand every
+    finished gradient to publish_grad, and autograd receives None."""
+
+    _mode = None
+
+    def _publish(self, param, grad):
+        publish_grad(self._comm, param, grad, self._mode)
+        return None
+
+
+def strategy_swap_map(mode, *mixins):
+    """The swap_map of a strategy that publishes in `mode`: each base module
+    under the publishing mixin, with `mixins` (ZeRO-3's gathers) in front."""
+    return {
+        torch_cls: type(base_cls.__name__, (*mixins, _PublishMixin, base_cls),
+                        {"_mode": mode})
+        for torch_cls, base_cls in ((nn.Linear, base.Linear),
+                                    (nn.LayerNorm, base.LayerNorm),
+                                    (nn.Embedding, base.Embedding))
+    }

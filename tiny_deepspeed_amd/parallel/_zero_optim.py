@@ -14,12 +14,16 @@ from .comm import default_comm
 class _ZeroOptimMixin:
     broadcast_params_after_step = True  # ZeRO-1/2; ZeRO-3 gathers JIT instead
 
-    def _setup_zero(self, param_part_table, ranks_map, comm):
+    def __init__(self, parameters, param_part_table=None, ranks_map=None,
+                 comm=None, **kw):
         if param_part_table is None:
             raise ValueError("param_part_table (partition) is required")
         self.comm = comm if comm is not None else default_comm()
         self.parts = dict(param_part_table)
         self.ranks_map = ranks_map
+        # ownership is set up first: the base constructor allocates state
+        # only where _owns_state says so
+        super().__init__(parameters, **kw)
 
     def _owner(self, name):
         return int(self.parts[name])

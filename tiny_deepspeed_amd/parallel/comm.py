@@ -88,8 +88,11 @@ class CommContext:
         self._works = {REDUCE: [], GATHER: []}
         self._keepalive = []
         # gloo flat broadcasts whose scatter-back is deferred to sync():
-        # (work, flat, bucket, numels) per channel
+        # (work, flat, bucket, src) per channel
         self._pending_flat = {REDUCE: [], GATHER: []}
+        # bumped by ZeRO-3 once per forward: gather buffers prefetched in an
+        # earlier iteration are stale
+        self.gather_epoch = 0
         # observability: per-collective launch counts and payload bytes
         # (read by bench.py's comm-stats line; negligible overhead)
         self.stats = {}
@@ -119,39 +122,43 @@ class CommContext:
             if work is not None:
                 self._works[channel].append(work)
 
-    def sync(self):
-        """Order subsequent compute after ALL outstanding communication.
-        Device-side wait on GPU (no host sync); work.wait() on gloo."""
-        for stream in self.streams.values():
-            if stream is not None:
-                torch.cuda.current_stream().wait_stream(stream)
-        for works in self._works.values():
-            for w in works:
+    def _wait(self, channels):
+        """Order subsequent compute after the channels' outstanding
+        communication. Device-side wait on GPU (no host sync); work.wait()
+        on gloo, each phase over all the channels before the next."""
+        for channel in channels:
+            if self.streams[channel] is not None:
+                torch.cuda.current_stream().wait_stream(self.streams[channel])
+        for channel in channels:
+            for w in self._works[channel]:
                 w.wait()
-            works.clear()
-        for channel in (REDUCE, GATHER):
+            self._works[channel].clear()
+        for channel in channels:
             self._drain_flat(channel)
+
+    def sync(self):
+        """Order subsequent compute after ALL outstanding communication."""
+        self._wait((REDUCE, GATHER))
         self._keepalive.clear()
 
     def wait_gather(self):
         """Order subsequent compute after outstanding gathers only."""
-        stream = self.streams[GATHER]
-        if stream is not None:
-            torch.cuda.current_stream().wait_stream(stream)
-        for w in self._works[GATHER]:
-            w.wait()
-        self._works[GATHER].clear()
-        self._drain_flat(GATHER)
+        self._wait((GATHER,))
+
+    def _scatter_back(self, flat, bucket, src):
+        """Copy a received flat broadcast into the bucket's tensors."""
+        if self.rank != src:
+            off = 0
+            for t in bucket:
+                n = t.numel()
+                t.view(-1).copy_(flat[off:off + n])
+                off += n
 
     def _drain_flat(self, channel):
         """Complete deferred gloo flat broadcasts: wait + scatter-back."""
-        for work, flat, bucket, numels, src in self._pending_flat[channel]:
+        for work, flat, bucket, src in self._pending_flat[channel]:
             work.wait()
-            if self.rank != src:
-                off = 0
-                for t, n in zip(bucket, numels):
-                    t.view(-1).copy_(flat[off:off + n])
-                    off += n
+            self._scatter_back(flat, bucket, src)
         self._pending_flat[channel].clear()
 
     def keep_until_sync(self, t):
@@ -239,21 +246,16 @@ class CommContext:
 
     def _broadcast_flat(self, bucket, src, channel):
         stream = self.streams[channel]
-        numels = [t.numel() for t in bucket]
         if self.rank == src:
             flat = torch.cat([t.reshape(-1) for t in bucket])
         else:
-            flat = torch.empty(sum(numels), dtype=bucket[0].dtype,
-                               device=bucket[0].device)
+            flat = torch.empty(sum(t.numel() for t in bucket),
+                               dtype=bucket[0].dtype, device=bucket[0].device)
         if stream is not None:
             stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(stream):
                 dist.broadcast(flat, src=src, group=self.pg[channel])
-                if self.rank != src:
-                    off = 0
-                    for t, n in zip(bucket, numels):
-                        t.view(-1).copy_(flat[off:off + n])
-                        off += n
+                self._scatter_back(flat, bucket, src)
                 flat.record_stream(stream)
                 for t in bucket:
                     t.record_stream(stream)
@@ -262,7 +264,7 @@ class CommContext:
             # to non-src ranks is deferred with the completion handle
             work = dist.broadcast(flat, src=src, group=self.pg[channel],
                                   async_op=True)
-            self._pending_flat[channel].append((work, flat, bucket, numels, src))
+            self._pending_flat[channel].append((work, flat, bucket, src))
 
     def reduce_scatter_avg(self, out_shard, in_flat):
         """Average-reduce `in_flat` (numel == world * shard) across ranks and

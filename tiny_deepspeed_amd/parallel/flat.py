@@ -24,23 +24,8 @@ import torch
 import torch.nn as nn
 
 from .. import optim as base_optim
-from ._grad import FLAT
-from .ddp import Linear as _DDPLinear
-from .ddp import LayerNorm as _DDPLayerNorm
-from .ddp import Embedding as _DDPEmbedding
+from ._grad import strategy_swap_map, FLAT
 from .wrapper import ModelWrapper
-
-
-class Linear(_DDPLinear):
-    _mode = FLAT
-
-
-class LayerNorm(_DDPLayerNorm):
-    _mode = FLAT
-
-
-class Embedding(_DDPEmbedding):
-    _mode = FLAT
 
 
 class _Bucket:
@@ -158,11 +143,7 @@ class FlatShardEngine:
 
 
 class Zero2Flat(ModelWrapper):
-    swap_map = {
-        nn.Linear: Linear,
-        nn.LayerNorm: LayerNorm,
-        nn.Embedding: Embedding,
-    }
+    swap_map = strategy_swap_map(FLAT)
 
     def __init__(self, module, comm=None, bucket_bytes=32 << 20):
         self._bucket_bytes = bucket_bytes
@@ -182,11 +163,12 @@ class _FlatOptimMixin:
     unchanged, just over shards (AdamW/SGD updates are elementwise, so
     shard-wise == tensor-wise exactly)."""
 
-    def _setup_flat(self, model):
+    def __init__(self, model, **kw):
         if not isinstance(model, Zero2Flat):
             raise TypeError("pass the Zero2Flat-wrapped model")
         self.engine = model.engine
         self.comm = model.comm
+        super().__init__(self._shard_params(self.engine), **kw)
 
     @staticmethod
     def _shard_params(engine):
@@ -222,12 +204,8 @@ class _FlatOptimMixin:
 
 
 class Zero2FlatAdamW(_FlatOptimMixin, base_optim.AdamW):
-    def __init__(self, model, **kw):
-        self._setup_flat(model)
-        super().__init__(self._shard_params(self.engine), **kw)
+    pass
 
 
 class Zero2FlatSGD(_FlatOptimMixin, base_optim.SGD):
-    def __init__(self, model, **kw):
-        self._setup_flat(model)
-        super().__init__(self._shard_params(self.engine), **kw)
+    pass

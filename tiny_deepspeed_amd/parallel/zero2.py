@@ -8,49 +8,22 @@ when RCCL is done (the reference could only shrink grad.data to 1 element
 and wished for a C++ plugin — zero2/module.py:26-36).
 """
 
-import torch.nn as nn
-
 from .. import optim as base_optim
-from ._grad import REDUCE_SHARD
+from ._grad import strategy_swap_map, REDUCE_SHARD
 from ._zero_optim import _ZeroOptimMixin
-from .ddp import Linear as _DDPLinear
-from .ddp import LayerNorm as _DDPLayerNorm
-from .ddp import Embedding as _DDPEmbedding
 from .wrapper import ModelWrapper
 
 
-class Linear(_DDPLinear):
-    _mode = REDUCE_SHARD
-
-
-class LayerNorm(_DDPLayerNorm):
-    _mode = REDUCE_SHARD
-
-
-class Embedding(_DDPEmbedding):
-    _mode = REDUCE_SHARD
-
-
 class Zero2(ModelWrapper):
-    swap_map = {
-        nn.Linear: Linear,
-        nn.LayerNorm: LayerNorm,
-        nn.Embedding: Embedding,
-    }
+    swap_map = strategy_swap_map(REDUCE_SHARD)
 
     def __init__(self, module, parts, comm=None):
         super().__init__(module, parts=parts, comm=comm)
 
 
 class Zero2SGD(_ZeroOptimMixin, base_optim.SGD):
-    def __init__(self, parameters, param_part_table=None, ranks_map=None,
-                 comm=None, **kw):
-        self._setup_zero(param_part_table, ranks_map, comm)
-        super().__init__(parameters, **kw)
+    pass
 
 
 class Zero2AdamW(_ZeroOptimMixin, base_optim.AdamW):
-    def __init__(self, parameters, param_part_table=None, ranks_map=None,
-                 comm=None, **kw):
-        self._setup_zero(param_part_table, ranks_map, comm)
-        super().__init__(parameters, **kw)
+    pass

@@ -26,10 +26,8 @@ import math
 import torch
 import torch.nn as nn
 
-from .. import modules as base
-from .. import ops
 from .. import optim as base_optim
-from ._grad import publish_grad, REDUCE_SHARD
+from ._grad import strategy_swap_map, REDUCE_SHARD
 from ._zero_optim import _ZeroOptimMixin
 from .wrapper import ModelWrapper
 
@@ -64,7 +62,7 @@ class _GatherMixin:
     def _issue_gathers(self):
         # epoch guard: buffers prefetched during backward must not survive
         # the optimizer step into the next forward (stale parameters)
-        epoch = getattr(self._comm, "gather_epoch", 0)
+        epoch = self._comm.gather_epoch
         if (getattr(self, "_tdsa_bufs", None) is None
                 or getattr(self, "_tdsa_buf_epoch", -1) != epoch):
             object.__setattr__(self, "_tdsa_bufs", {
@@ -85,74 +83,14 @@ class _GatherMixin:
         return bufs
 
 
-class Linear(_GatherMixin, base.Linear):
-    # fused lm_head+CE hooks: consume the JIT-gathered full weight in both
-    # directions; dW is averaged-reduced to the owner and dropped elsewhere
-    def _ce_weight_fwd(self):
-        return self._take_bufs("_tdsa_next")["weight"]
+    # the base callbacks' parameter hooks: the gather buffers they return
+    # die with the callback; the allocator reclaims them stream-safely
+    def _params_fwd(self):
+        bufs = self._take_bufs("_tdsa_next")
+        return bufs["weight"], bufs["bias"]
 
-    def _ce_weight_bwd(self):
+    def _weight_bwd(self):
         return self._take_bufs("_tdsa_prev")["weight"]
-
-    def publish_weight_grad(self, dw):
-        publish_grad(self._comm, self.weight, dw, REDUCE_SHARD)
-        return None
-
-    def forward_callback(self, x, weight, bias):
-        bufs = self._take_bufs("_tdsa_next")
-        return ops.linear_forward(x, bufs["weight"], bufs["bias"],
-                                  tuner=self.tuner)
-        # gather buffers die here; the allocator reclaims them stream-safely
-
-    def backward_callback(self, dy, x):
-        w = self._take_bufs("_tdsa_prev")["weight"]
-        if self.weight.requires_grad:
-            dw = ops.linear_weight_grad(dy, x, tuner=self.tuner)
-            assert tuple(dw.shape) == self.weight._tdsa_full_shape
-            publish_grad(self._comm, self.weight, dw, REDUCE_SHARD)
-        if self.bias is not None and self.bias.requires_grad:
-            db = ops.linear_bias_grad(dy, tuner=self.tuner)
-            publish_grad(self._comm, self.bias, db, REDUCE_SHARD)
-        dx = ops.linear_input_grad(dy, w, tuner=self.tuner)
-        return dx, None, None
-
-
-class LayerNorm(_GatherMixin, base.LayerNorm):
-    def forward_callback(self, x, weight, bias):
-        bufs = self._take_bufs("_tdsa_next")
-        return ops.layernorm_fwd(x, bufs["weight"], bufs["bias"],
-                                 eps=self.eps, tuner=self.tuner)
-
-    def forward_res_callback(self, x, res, weight, bias):
-        bufs = self._take_bufs("_tdsa_next")
-        return ops.layernorm_fwd_res(x, res, bufs["weight"], bufs["bias"],
-                                     eps=self.eps, tuner=self.tuner)
-
-    def backward_callback(self, dy, x, mean, rstd, dh=None):
-        w = self._take_bufs("_tdsa_prev")["weight"]
-        dx, ws = ops.layernorm_dx(dy, x, w, mean, rstd, dh=dh,
-                                  tuner=self.tuner)
-        if self.weight.requires_grad:
-            dw, db = ops.layernorm_dwdb(ws, dtype=self.weight.dtype,
-                                        tuner=self.tuner)
-            publish_grad(self._comm, self.weight, dw, REDUCE_SHARD)
-            publish_grad(self._comm, self.bias, db, REDUCE_SHARD)
-        return dx, None, None
-
-
-class Embedding(_GatherMixin, base.Embedding):
-    def forward_callback(self, idx, weight):
-        w = self._take_bufs("_tdsa_next")["weight"]
-        return ops.embedding_forward(w, idx, padding_idx=self.padding_idx,
-                                     tuner=self.tuner)
-
-    def backward_callback(self, dy, idx):
-        if self.weight.requires_grad:
-            dw = ops.embedding_weight_grad(idx, dy, self.num_embeddings,
-                                           padding_idx=self.padding_idx,
-                                           tuner=self.tuner)
-            publish_grad(self._comm, self.weight, dw, REDUCE_SHARD)
-        return None
 
 
 def _rebind(mod, pname, old_param, new_data):
@@ -189,18 +127,15 @@ def _materialize(mod, pname, shape, dtype, device):
 
 
 class Zero3(ModelWrapper):
-    swap_map = {
-        nn.Linear: Linear,
-        nn.LayerNorm: LayerNorm,
-        nn.Embedding: Embedding,
-    }
+    # gradients are average-reduced to the owner and dropped elsewhere
+    swap_map = strategy_swap_map(REDUCE_SHARD, _GatherMixin)
 
     def __init__(self, module, parts, comm=None, device=None):
         self._shard_device = device
         super().__init__(module, parts=parts, comm=comm)
 
     def forward(self, *args, **kwargs):
-        self.comm.gather_epoch = getattr(self.comm, "gather_epoch", 0) + 1
+        self.comm.gather_epoch += 1
         return super().forward(*args, **kwargs)
 
     def _post_wrap(self):
@@ -250,14 +185,8 @@ class _Zero3OptimMixin(_ZeroOptimMixin):
 
 
 class Zero3SGD(_Zero3OptimMixin, base_optim.SGD):
-    def __init__(self, parameters, param_part_table=None, ranks_map=None,
-                 comm=None, **kw):
-        self._setup_zero(param_part_table, ranks_map, comm)
-        super().__init__(parameters, **kw)
+    pass
 
 
 class Zero3AdamW(_Zero3OptimMixin, base_optim.AdamW):
-    def __init__(self, parameters, param_part_table=None, ranks_map=None,
-                 comm=None, **kw):
-        self._setup_zero(param_part_table, ranks_map, comm)
-        super().__init__(parameters, **kw)
+    pass
