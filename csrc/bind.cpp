@@ -500,6 +500,36 @@ at::Tensor gemm_tn(at::Tensor dy2, at::Tensor x2) {
   return (splits > 1 ? dw32.sum(0) : dw32.select(0, 0)).to(at::kBFloat16);
 }
 
+// ---- transpose / linear dX in the forward's GEMM layout -------------------
+// out[K, N] = w[N, K]^T, bit for bit.
+at::Tensor transpose_bf16(at::Tensor w) {
+  const char* op = "transpose_bf16";
+  check_call(op, {{"w", w, at::kBFloat16, kAny}});
+  TORCH_CHECK(w.dim() == 2, op, ": w must be 2-D, got ", w.sizes());
+  const long long N = w.size(0), K = w.size(1);
+  TORCH_CHECK(N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0, op,
+              ": both dims must be positive multiples of 64, got ", w.sizes());
+  auto out = at::empty({K, N}, w.options());
+  check_hip(tdsa_transpose_bf16(w.data_ptr(), out.data_ptr(), N, K,
+                                cur_stream()),
+            op);
+  return out;
+}
+
+// dx[M, K] = dy2[M, N] @ w[N, K] as the library's forward-layout GEMM: w is
+// transposed on the fly (never kept: the weight may change between calls) and
+// the product goes through at::linear, so TunableOp and its cache apply.
+at::Tensor linear_dx_nt(at::Tensor dy2, at::Tensor w) {
+  const char* op = "linear_dx_nt";
+  check_call(op, {{"dy2", dy2, at::kBFloat16, kAny},
+                  {"w", w, at::kBFloat16, kAny}});
+  TORCH_CHECK(dy2.dim() == 2 && w.dim() == 2, op, " expects 2-D inputs, got ",
+              dy2.sizes(), " and ", w.sizes());
+  TORCH_CHECK(dy2.size(1) == w.size(0), op, ": dy2 ", dy2.sizes(),
+              " does not contract with w ", w.sizes());
+  return at::linear(dy2, transpose_bf16(w));
+}
+
 // ---- attention ------------------------------------------------------------
 // One pass over an attention call's bf16 tensors, q first. The kernels use
 // q's extents and, per group, one tensor's strides (`lead`: q for q/k/v, o for
@@ -640,6 +670,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("n_valid"), py::arg("ignore_index"),
           py::arg("out") = py::none());
   mod.def("gemm_tn", &gemm_tn);
+  mod.def("transpose_bf16", &transpose_bf16);
+  mod.def("linear_dx_nt", &linear_dx_nt);
   mod.def("adamw_step_multi", &adamw_step_multi, py::arg("params"),
           py::arg("grads"), py::arg("ms"), py::arg("vs"), py::arg("masters"),
           py::arg("vmaxs"), py::arg("lr"), py::arg("b1"), py::arg("b2"),

@@ -134,6 +134,12 @@ int tdsa_gemm_tn_splits(long long M, int N, int K);
 hipError_t tdsa_gemm_tn(const void* dy, const void* x, float* dw, long long M,
                         int N, int K, hipStream_t stream);
 
+// ---- transpose.hip ----------------------------------------------------------
+// out bf16 [K, N] = in bf16 [N, K] transposed; N and K multiples of 64. in and
+// out must not overlap.
+hipError_t tdsa_transpose_bf16(const void* in, void* out, long long N,
+                               long long K, hipStream_t stream);
+
 // ---- debug.hip --------------------------------------------------------------
 // Fragment-layout probes on one wave. A [16, 32], B [32, 16] bf16 -> D fp32
 // [16, 16]; variant picks the A/B fragment layout.

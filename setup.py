@@ -24,6 +24,7 @@ SOURCES = [
     "csrc/kernels/gradnorm.hip",
     "csrc/kernels/attention.hip",
     "csrc/kernels/gemm_tn.hip",
+    "csrc/kernels/transpose.hip",
     "csrc/kernels/debug.hip",
 ]
 

@@ -7,16 +7,22 @@ each op owns a list of implementations and routes through the runtime
 autotuner, which times them per shape and caches the winner.
 
   fwd : out[M,N] = x[M,K] @ W[N,K]^T (+ b)      (NT GEMM — hipBLASLt)
-  dX  : dx[M,K]  = dy[M,N] @ W[N,K]             (NN GEMM — hipBLASLt)
+  dX  : dx[M,K]  = dy[M,N] @ W[N,K]             ({CDNA4 transpose of W +
+                                                 the forward's NT GEMM,
+                                                 NN GEMM — hipBLASLt}, tuned)
   dW  : dw[N,K]  = dy[M,N]^T @ x[M,K]           (TN GEMM — {CDNA4 MFMA
                                                  kernel, hipBLASLt}, tuned)
   db  : db[N]    = sum_M dy[M,N]                ({CDNA4 column_sum, torch})
 
-MI355X design note: the plain NT/NN GEMMs stay on the library path —
+MI355X design note: the forward NT GEMM stays on the library path —
 measured at the practical MFMA ceiling (profiles/gemm_shapes_hipblaslt.txt,
 fwd NT 1436 TF/s) — while dW (TN, the weakest library shape) carries a
 hand-written split-M MFMA kernel as a tuner candidate so the question is
-settled by measurement per shape, not by assertion.
+settled by measurement per shape, not by assertion. dX as an NN GEMM gets
+the library's smaller tiles; with W^T made row-major first (one native
+transpose per call, never cached, so no strategy can see a stale copy) it is
+the forward's layout again, and the tuner times both per shape, transpose
+included (profiles/linear_dx.txt).
 """
 
 import os
@@ -39,8 +45,49 @@ def linear_forward(x, weight, bias=None, tuner=None):
     return out
 
 
+# --- dX candidates ---------------------------------------------------------
+def dx_library(dy2, weight):
+    """hipBLASLt NN GEMM via torch.matmul."""
+    return torch.matmul(dy2, weight)
+
+
+def dx_nt(dy2, weight):
+    """W^T by the CDNA4 transpose kernel (csrc/kernels/transpose.hip), made
+    for this call only, then the library's forward-layout GEMM."""
+    return _ext.get_ext().linear_dx_nt(dy2.contiguous(), weight)
+
+
+def _dx_nt_supported(dy2, weight):
+    if os.environ.get("TDSA_LINEAR_DX", "1") == "0":
+        return False
+    if not _ext.ext_available() or not hasattr(_ext.get_ext(), "linear_dx_nt"):
+        return False
+    # kernel contract (csrc/kernels/transpose.hip): bf16 [N, K] contiguous
+    # with N % 64 == 0 and K % 64 == 0 — every GPT-2 preset's widths and the
+    # padded vocabulary
+    return (
+        dy2.dtype == torch.bfloat16
+        and weight.dtype == torch.bfloat16
+        and weight.dim() == 2
+        and weight.is_contiguous()
+        and weight.shape[0] % 64 == 0
+        and weight.shape[1] % 64 == 0
+    )
+
+
 def linear_input_grad(dy, weight, tuner=None):
-    return torch.matmul(dy, weight)
+    if not dy.is_cuda or weight.dim() != 2:
+        return torch.matmul(dy, weight)
+    dy2 = _flatten_batch(dy)
+    candidates = [dx_library]
+    if _ext.use_native(dy2) and _dx_nt_supported(dy2, weight):
+        candidates.insert(0, dx_nt)
+    tuner = tuner if tuner is not None else default_tuner()
+    if tuner is not None:
+        dx2 = tuner.choose("linear_dx", candidates, dy2, weight)
+    else:
+        dx2 = candidates[0](dy2, weight)
+    return dx2.view(*dy.shape[:-1], weight.shape[-1])
 
 
 # --- dW candidates ---------------------------------------------------------
