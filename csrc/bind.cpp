@@ -534,9 +534,10 @@ at::Tensor linear_dx_nt(at::Tensor dy2, at::Tensor w) {
 // One pass over an attention call's bf16 tensors, q first. The kernels use
 // q's extents and, per group, one tensor's strides (`lead`: q for q/k/v, o for
 // o/dout, dq for dq/dk/dv), so any other shape or stride stops here.
+// ragged: the attention_ragged_* entry points, any T >= 1.
 struct AttnTensor { const char* name; const at::Tensor &t, &lead; };
 static void check_attn_call(std::initializer_list<AttnTensor> tensors,
-                            double dropout_p) {
+                            double dropout_p, bool ragged) {
   const at::Tensor& q = tensors.begin()->t;
   for (const auto& [name, t, lead] : tensors) {
     TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
@@ -549,7 +550,11 @@ static void check_attn_call(std::initializer_list<AttnTensor> tensors,
     TORCH_CHECK(t.strides() == lead.strides(), name,
                 ": q/k/v, o/dout and dq/dk/dv must each share strides");
   }
-  TORCH_CHECK(q.size(2) % 64 == 0, "attention kernel requires T % 64 == 0");
+  if (ragged) {
+    TORCH_CHECK(q.size(2) >= 1, "attention kernel requires T >= 1");
+  } else {
+    TORCH_CHECK(q.size(2) % 64 == 0, "attention kernel requires T % 64 == 0");
+  }
   TORCH_CHECK(dropout_p >= 0.0 && dropout_p < 1.0, "bad dropout_p");
 }
 
@@ -557,13 +562,13 @@ static std::array<long long, 3> strides3(const at::Tensor& t) {
   return {t.stride(0), t.stride(1), t.stride(2)};
 }
 
-std::vector<at::Tensor> attention_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                                      double scale,
-                                      c10::optional<at::Tensor> out,
-                                      double dropout_p, int64_t seed) {
+static std::vector<at::Tensor> attn_fwd_call(
+    const char* op, bool ragged, at::Tensor q, at::Tensor k, at::Tensor v,
+    double scale, c10::optional<at::Tensor> out, double dropout_p,
+    int64_t seed) {
   at::Tensor o = out.has_value() ? *out : at::empty_like(q);
   check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"out", o, o}},
-                  dropout_p);
+                  dropout_p, ragged);
   const long long B = q.size(0), H = q.size(1), T = q.size(2);
   auto lse = at::empty({B, H, T}, q.options().dtype(at::kFloat));
   check_hip(tdsa_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
@@ -571,23 +576,38 @@ std::vector<at::Tensor> attention_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                           (float)scale, strides3(q).data(), strides3(o).data(),
                           (float)dropout_p, (unsigned long long)seed,
                           cur_stream()),
-            "attention_fwd");
+            op);
   return {o, lse};
 }
 
-std::vector<at::Tensor> attention_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                                      at::Tensor o, at::Tensor lse,
-                                      at::Tensor dout, double scale,
-                                      c10::optional<at::Tensor> dq_out,
-                                      c10::optional<at::Tensor> dk_out,
-                                      c10::optional<at::Tensor> dv_out,
+// T % 64 == 0 only (the aligned kernels); attention_ragged_fwd takes any
+// T >= 1 and, for T % 64 == 0, runs the same kernels.
+std::vector<at::Tensor> attention_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
+                                      double scale,
+                                      c10::optional<at::Tensor> out,
                                       double dropout_p, int64_t seed) {
+  return attn_fwd_call("attention_fwd", false, q, k, v, scale, out, dropout_p,
+                       seed);
+}
+
+std::vector<at::Tensor> attention_ragged_fwd(
+    at::Tensor q, at::Tensor k, at::Tensor v, double scale,
+    c10::optional<at::Tensor> out, double dropout_p, int64_t seed) {
+  return attn_fwd_call("attention_ragged_fwd", true, q, k, v, scale, out,
+                       dropout_p, seed);
+}
+
+static std::vector<at::Tensor> attn_bwd_call(
+    const char* op, bool ragged, at::Tensor q, at::Tensor k, at::Tensor v,
+    at::Tensor o, at::Tensor lse, at::Tensor dout, double scale,
+    c10::optional<at::Tensor> dq_out, c10::optional<at::Tensor> dk_out,
+    c10::optional<at::Tensor> dv_out, double dropout_p, int64_t seed) {
   at::Tensor dq = dq_out.has_value() ? *dq_out : at::empty_like(q);
   at::Tensor dk = dk_out.has_value() ? *dk_out : at::empty_like(k);
   at::Tensor dv = dv_out.has_value() ? *dv_out : at::empty_like(v);
   check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"o", o, o},
                    {"dout", dout, o}, {"dq", dq, dq}, {"dk", dk, dq},
-                   {"dv", dv, dq}}, dropout_p);
+                   {"dv", dv, dq}}, dropout_p, ragged);
   const long long B = q.size(0), H = q.size(1), T = q.size(2);
   TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
                   lse.numel() == B * H * T,
@@ -601,8 +621,28 @@ std::vector<at::Tensor> attention_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                           strides3(q).data(), strides3(o).data(),
                           strides3(dq).data(), (float)dropout_p,
                           (unsigned long long)seed, cur_stream()),
-            "attention_bwd");
+            op);
   return {dq, dk, dv};
+}
+
+std::vector<at::Tensor> attention_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
+                                      at::Tensor o, at::Tensor lse,
+                                      at::Tensor dout, double scale,
+                                      c10::optional<at::Tensor> dq_out,
+                                      c10::optional<at::Tensor> dk_out,
+                                      c10::optional<at::Tensor> dv_out,
+                                      double dropout_p, int64_t seed) {
+  return attn_bwd_call("attention_bwd", false, q, k, v, o, lse, dout, scale,
+                       dq_out, dk_out, dv_out, dropout_p, seed);
+}
+
+std::vector<at::Tensor> attention_ragged_bwd(
+    at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
+    at::Tensor dout, double scale, c10::optional<at::Tensor> dq_out,
+    c10::optional<at::Tensor> dk_out, c10::optional<at::Tensor> dv_out,
+    double dropout_p, int64_t seed) {
+  return attn_bwd_call("attention_ragged_bwd", true, q, k, v, o, lse, dout,
+                       scale, dq_out, dk_out, dv_out, dropout_p, seed);
 }
 
 // ---- debug probes ---------------------------------------------------------
@@ -689,6 +729,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("attention_bwd", &attention_bwd, py::arg("q"), py::arg("k"),
           py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("dout"),
           py::arg("scale"), py::arg("dq") = py::none(),
+          py::arg("dk") = py::none(), py::arg("dv") = py::none(),
+          py::arg("dropout_p") = 0.0, py::arg("seed") = 0);
+  mod.def("attention_ragged_fwd", &attention_ragged_fwd, py::arg("q"),
+          py::arg("k"), py::arg("v"), py::arg("scale"),
+          py::arg("out") = py::none(), py::arg("dropout_p") = 0.0,
+          py::arg("seed") = 0);
+  mod.def("attention_ragged_bwd", &attention_ragged_bwd, py::arg("q"),
+          py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"),
+          py::arg("dout"), py::arg("scale"), py::arg("dq") = py::none(),
           py::arg("dk") = py::none(), py::arg("dv") = py::none(),
           py::arg("dropout_p") = 0.0, py::arg("seed") = 0);
 }

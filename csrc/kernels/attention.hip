@@ -64,8 +64,9 @@
 //   B[16x32]: lane l, elem e      -> B[(l/32)*8 + e][l%32]
 //   C[32x32]: lane l, reg r(0..15)-> C[(r&3) + 8*(r>>2) + 4*(l/32)][l%32]
 //
-// Contract: bf16, head_dim 64, T % 64 == 0 (the Python op falls back to a
-// composite rocBLAS path otherwise, ops/attention.py).
+// Contract: bf16, head_dim 64, any T >= 1. T % 64 == 0 runs the kernels as
+// described above; any other T their tail variants ("Ragged T" below), which
+// handle the partial last tile and read or write no row >= T.
 #include "common.h"
 #include "launchers.h"
 #include "mfma.h"
@@ -216,19 +217,47 @@ struct FragOff {
 //               <compute on lds_a / lds_b> }
 // Per-tile side inputs ride along as a companion (RowPipe, below), so that
 // no load-and-use sits between next() and the barrier.
-template <int NT>
-struct TilePipe {
+//
+// TAIL (ragged T): `left` is the number of rows that the pending pair has in
+// memory, counted from its first row; the constructor takes it for the first
+// pair. A pair with left >= KVB is fetched as in the aligned kernels; the one
+// pair that holds row T-1 takes the predicated fetch (a block-uniform
+// branch, so whole tiles pay one scalar compare), reads no row >= T and puts
+// zeros in their place. The tail's state is an empty base in the aligned
+// kernels: as plain members that they never read it still changed the
+// register allocation of the 4-wave dkv kernel.
+template <bool TAIL>
+struct TailRows {
+  DEV_INLINE TailRows(int, int) {}
+};
+template <>
+struct TailRows<true> {
+  int tid, left;
+  DEV_INLINE TailRows(int tid, int left) : tid(tid), left(left) {}
+};
+
+template <int NT, bool TAIL = false>
+struct TilePipe : TailRows<TAIL> {
   Stage<NT> a, b;
   short8v pend_a[Stage<NT>::REPS], pend_b[Stage<NT>::REPS];
 
   DEV_INLINE TilePipe(const bf16* ga, int st_a, const bf16* gb, int st_b,
-                      int tid)
-      : a(ga, tid, st_a), b(gb, tid, st_b) {}
+                      int tid, int left = 0)
+      : TailRows<TAIL>(tid, left), a(ga, tid, st_a), b(gb, tid, st_b) {}
 
-  DEV_INLINE void prime() {
+  DEV_INLINE void fetch() {
+    if constexpr (TAIL) {
+      if (this->left < KVB) {
+        a.fetch_rows(pend_a, this->tid, this->left);
+        b.fetch_rows(pend_b, this->tid, this->left);
+        return;
+      }
+    }
     a.fetch(pend_a);
     b.fetch(pend_b);
   }
+
+  DEV_INLINE void prime() { fetch(); }
 
   // Barrier (the previous pair is consumed), pending registers -> LDS, and
   // with `more` the loads of the following pair. The caller places the
@@ -250,8 +279,8 @@ struct TilePipe {
     if (more) {
       a.advance();
       b.advance();
-      a.fetch(pend_a);
-      b.fetch(pend_b);
+      if constexpr (TAIL) this->left -= KVB;
+      fetch();
       rows.advance();
       rows.fetch();
     }
@@ -269,6 +298,9 @@ struct TilePipe {
 // tile ahead in two registers and publishes a[r] * mul_a and b[r] to LDS.
 //   pipe.prime(); rows.fetch();
 //   for (...) { pipe.next(lds_a, lds_b, more, rows); __syncthreads(); ... }
+// TAIL (ragged T): `left` rows of the pending tile exist; a later row is not
+// read and carries a = +inf (lse: P = exp2(s - inf) is exactly 0) and b = 0.
+template <bool TAIL = false>
 struct RowPipe {
   const float* ga;   // the pending tile's first row (block-uniform)
   const float* gb;
@@ -276,14 +308,25 @@ struct RowPipe {
   float* lds_b;
   float mul_a;
   int tid;
+  int left;   // TAIL only
   float pend_a, pend_b;
 
   DEV_INLINE RowPipe(const float* ga, const float* gb, float* lds_a,
-                     float* lds_b, float mul_a, int tid)
-      : ga(ga), gb(gb), lds_a(lds_a), lds_b(lds_b), mul_a(mul_a), tid(tid) {}
+                     float* lds_b, float mul_a, int tid, int left = 0)
+      : ga(ga), gb(gb), lds_a(lds_a), lds_b(lds_b), mul_a(mul_a), tid(tid),
+        left(left) {}
 
   DEV_INLINE void fetch() {
-    if (tid < KVB) {
+    if constexpr (TAIL) {
+      if (tid < KVB) {
+        pend_a = INFINITY;
+        pend_b = 0.f;
+        if (tid < left) {
+          pend_a = ga[tid];
+          pend_b = gb[tid];
+        }
+      }
+    } else if (tid < KVB) {
       pend_a = ga[tid];
       pend_b = gb[tid];
     }
@@ -299,6 +342,7 @@ struct RowPipe {
   DEV_INLINE void advance() {
     ga += KVB;
     gb += KVB;
+    if constexpr (TAIL) left -= KVB;
   }
 };
 
@@ -368,6 +412,25 @@ DEV_INLINE bfrag load_frag(const bf16* p, int row, int col, int st) {
   return r.f;
 }
 
+// TAIL (ragged T): the fragment of a row that does not exist (`ok` false) is
+// not read and is all zeros; a zero row scaled is a zero row.
+template <bool TAIL>
+DEV_INLINE bfrag load_frag_scaled(const bf16* p, int row, int col, int st,
+                                  float s, bool ok) {
+  if constexpr (TAIL) {
+    if (!ok) return bfrag{};
+  }
+  return load_frag_scaled(p, row, col, st, s);
+}
+
+template <bool TAIL>
+DEV_INLINE bfrag load_frag(const bf16* p, int row, int col, int st, bool ok) {
+  if constexpr (TAIL) {
+    if (!ok) return bfrag{};
+  }
+  return load_frag(p, row, col, st);
+}
+
 // Epilogue of one wave's 32x64 result, held as two C tiles: element
 // (crow(r,h32), 32*dt + x32) = acc[dt][r] * mul(r), stored as bf16 at row
 // stride st from p (the wave's first row).
@@ -380,6 +443,8 @@ DEV_INLINE bfrag load_frag(const bf16* p, int row, int col, int st) {
 // Banks: a ds_write_b16 group is one half-wave = 64 contiguous bytes of one
 // row; a ds_read_b128 group of 16 lanes covers four 64-byte half rows whose
 // offsets mod 256 are all different. Neither needs padding or a swizzle.
+// TAIL (ragged T): only the wave's first `rows` rows (any value; <= 0: none)
+// exist and are stored.
 constexpr int STAGE_BYTES = 32 * D * 2;
 
 // Orders a wave's LDS writes before its own later LDS reads (and the other
@@ -391,9 +456,10 @@ DEV_INLINE void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <typename F>
+template <bool TAIL = false, typename F>
 DEV_INLINE void store_ctiles(bf16* p, int st, const BlockCtx& c,
-                             const f32x16 (&acc)[2], F mul, char* stage) {
+                             const f32x16 (&acc)[2], F mul, char* stage,
+                             int rows = 32) {
   bf16* img = reinterpret_cast<bf16*>(stage);
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
@@ -405,6 +471,9 @@ DEV_INLINE void store_ctiles(bf16* p, int st, const BlockCtx& c,
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int row = 8 * i + (c.lane >> 3);
+    if constexpr (TAIL) {
+      if (row >= rows) continue;
+    }
     store8(p + row * st + piece * 8,
            *reinterpret_cast<const short8v*>(stage + row * (D * 2) +
                                              piece * 16));
@@ -427,10 +496,11 @@ constexpr int fwd_min_blocks(int nw, bool drop) {
 // One Q block (c.tile) of the forward; the kernel below calls it once per
 // pass. Everything but `c` and the LDS is re-created per pass; the first
 // pipe.next() of a pass holds the barrier that ends the previous pass's reads.
-template <int NW, bool DROP>
+template <int NW, bool DROP, bool TAIL>
 // DROP: fused attention dropout — the row sum l_run uses the UNMASKED
 // exponentials (normalization is the true softmax sum) while the PV
 // accumulation consumes masked/rescaled P.
+// TAIL: ragged T, see "Ragged T" above the tail kernels.
 DEV_INLINE void attn_fwd_tile(const BlockCtx& c, char* smem,
                               const bf16* __restrict__ q,
                               const bf16* __restrict__ k,
@@ -446,7 +516,10 @@ DEV_INLINE void attn_fwd_tile(const BlockCtx& c, char* smem,
   const long long boff = c.base(sq, H);
   const bf16* qp = q + boff + (long long)(c.tile * BM) * sq.t;
 
-  TilePipe<NT> pipe(k + boff, sq.t, v + boff, sq.t, c.tid);
+  const int row_lo = c.tile * BM + c.w * 32;
+  const int row_me = row_lo + c.x32;
+
+  TilePipe<NT, TAIL> pipe(k + boff, sq.t, v + boff, sq.t, c.tid, T);
   const FragOff kf(c);
   int trb[2][2];
   tr_bases(c.lane, trb);
@@ -454,16 +527,15 @@ DEV_INLINE void attn_fwd_tile(const BlockCtx& c, char* smem,
   bfrag q_frag[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s)
-    q_frag[s] = load_frag_scaled(qp, c.w * 32 + c.x32, s * 16 + 8 * c.h32,
-                                 sq.t, qscale);
+    q_frag[s] = load_frag_scaled<TAIL>(qp, c.w * 32 + c.x32,
+                                       s * 16 + 8 * c.h32, sq.t, qscale,
+                                       row_me < T);
 
   const f32x16 kzero = {};
   f32x16 o_acc[2] = {};
   float m_run = -INFINITY;
   float l_run = 0.f;
 
-  const int row_lo = c.tile * BM + c.w * 32;
-  const int row_me = row_lo + c.x32;
   // dropout index base (loop-invariant): idx = base + key
   const unsigned long long drop_base =
       DROP ? ((unsigned long long)c.bh * T + row_me) * T : 0;
@@ -475,6 +547,9 @@ DEV_INLINE void attn_fwd_tile(const BlockCtx& c, char* smem,
 
     const int key0 = j * KVB;
     if (key0 > row_lo + 31) continue;
+    if constexpr (TAIL) {
+      if (row_lo >= T) continue;   // a wave of padded rows only
+    }
 
     // S^T tiles: C[key = 32*t2 + crow(r,h32)][qrow = x32], log2-scaled
     f32x16 st[2];
@@ -567,10 +642,10 @@ DEV_INLINE void attn_fwd_tile(const BlockCtx& c, char* smem,
   for (int r = 0; r < 16; ++r)
     linv_row[r] = fast_rcp(__shfl(l_run, crow(r, e.h32), WAVE));
   const int erow_lo = e.tile * BM + e.w * 32;
-  store_ctiles(o + e.base(so, H) + (long long)erow_lo * so.t, so.t, e, o_acc,
-               [&](int r) { return linv_row[r]; },
-               smem + 2 * KVB * D * 2 + e.w * STAGE_BYTES);
-  if (e.lane < 32) {
+  store_ctiles<TAIL>(o + e.base(so, H) + (long long)erow_lo * so.t, so.t, e,
+                     o_acc, [&](int r) { return linv_row[r]; },
+                     smem + 2 * KVB * D * 2 + e.w * STAGE_BYTES, T - erow_lo);
+  if (e.lane < 32 && (!TAIL || erow_lo + e.x32 < T)) {
     lse[e.bh * T + erow_lo + e.x32] = (m_run + log2f(l_run)) * LN2;
   }
 }
@@ -592,8 +667,49 @@ __global__ void attn_fwd_kernel(const bf16* __restrict__ q,
   __shared__ __attribute__((aligned(16))) char smem[attn_lds_bytes(NW)];
   BlockCtx c(T / (NW * 32), balance, true);
   do {
-    attn_fwd_tile<NW, DROP>(c, smem, q, k, v, o, lse, T, H, scale, sq, so,
-                            drop);
+    attn_fwd_tile<NW, DROP, false>(c, smem, q, k, v, o, lse, T, H, scale, sq,
+                                   so, drop);
+  } while (c.next_pass());
+}
+
+// Ragged T (T % 64 != 0): the tail kernels. They are the kernels above with
+// TAIL set in their tile functions, on ceil(T / (NW*32)) blocks along T, NW
+// chosen for T rounded up to 64 (so NW*32 divides that, and the last K/V or
+// Q/dO tile of every loop is the one tile that holds row T-1). Rows >= T of a
+// (batch, head) do not exist: in the packed layout "row T" is row 0 of the
+// next batch. So
+//   - no global read touches a row >= T: staged chunks (TilePipe), pinned
+//     fragments (load_frag*<TAIL>) and lse/delta (RowPipe<TAIL>, dq prologue)
+//     are predicated and arrive as zeros (lse: +inf);
+//   - nothing is stored to a row >= T (store_ctiles<TAIL>, lse, delta);
+//   - a wave whose 32 rows (keys in dkv) are all >= T skips its compute and
+//     keeps its barriers, like a wave above the diagonal.
+// A padded key is above the diagonal of every row < T, and a padded row adds
+// P = 0, dS = 0 times Q = 0, dO = 0 to dK/dV of the keys < T: exact zeros,
+// so rows < T carry the bits of the aligned kernels on the zero-padded
+// problem. Separate __global__ functions: they take their own launch bounds
+// and are compiled without packed fp32 math (TAIL_TARGET).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TAIL_TARGET __attribute__((target("no-packed-fp32-ops")))
+#else
+#define TAIL_TARGET
+#endif
+
+template <int NW, bool DROP = false>
+__launch_bounds__(NW * WAVE, fwd_min_blocks(NW, DROP))
+TAIL_TARGET
+__global__ void attn_fwd_tail_kernel(const bf16* __restrict__ q,
+                                     const bf16* __restrict__ k,
+                                     const bf16* __restrict__ v,
+                                     bf16* __restrict__ o,
+                                     float* __restrict__ lse, int T, int H,
+                                     float scale, GStride sq, GStride so,
+                                     Dropout drop, int balance) {
+  __shared__ __attribute__((aligned(16))) char smem[attn_lds_bytes(NW)];
+  BlockCtx c((T + NW * 32 - 1) / (NW * 32), balance, true);
+  do {
+    attn_fwd_tile<NW, DROP, true>(c, smem, q, k, v, o, lse, T, H, scale, sq,
+                                  so, drop);
   } while (c.next_pass());
 }
 
@@ -601,7 +717,7 @@ __global__ void attn_fwd_kernel(const bf16* __restrict__ q,
 // Backward dK/dV: one workgroup per (NW*32)-key block; wave w owns 32 keys.
 // ---------------------------------------------------------------------------
 // One key block (c.tile, c.x32: key in wave) of dK/dV, called once per pass.
-template <int NW, bool DROP>
+template <int NW, bool DROP, bool TAIL>
 DEV_INLINE void attn_bwd_dkv_tile(const BlockCtx& c, char* smem,
                                   const bf16* __restrict__ q,
                                   const bf16* __restrict__ k,
@@ -625,9 +741,9 @@ DEV_INLINE void attn_bwd_dkv_tile(const BlockCtx& c, char* smem,
   const long long boff = c.base(sq, H);
   const int i0 = c.tile * BK / KVB;   // first Q tile that sees these keys
 
-  TilePipe<NT> pipe(q + boff + (long long)(i0 * KVB) * sq.t, sq.t,
-                    dout + c.base(so, H) + (long long)(i0 * KVB) * so.t, so.t,
-                    c.tid);
+  TilePipe<NT, TAIL> pipe(q + boff + (long long)(i0 * KVB) * sq.t, sq.t,
+                          dout + c.base(so, H) + (long long)(i0 * KVB) * so.t,
+                          so.t, c.tid, T - i0 * KVB);
   const FragOff af(c);
   int trb[2][2];
   tr_bases(c.lane, trb);
@@ -640,9 +756,10 @@ DEV_INLINE void attn_bwd_dkv_tile(const BlockCtx& c, char* smem,
   bfrag k_frag[4], v_frag[4];  // B operands: col = x32, k-slices over D
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    k_frag[s] = load_frag_scaled(k + boff, key_me, s * 16 + 8 * c.h32, sq.t,
-                                 kscale);
-    v_frag[s] = load_frag(v + boff, key_me, s * 16 + 8 * c.h32, sq.t);
+    k_frag[s] = load_frag_scaled<TAIL>(k + boff, key_me, s * 16 + 8 * c.h32,
+                                       sq.t, kscale, key_me < T);
+    v_frag[s] = load_frag<TAIL>(v + boff, key_me, s * 16 + 8 * c.h32, sq.t,
+                                key_me < T);
   }
 
   const f32x16 kzero = {};
@@ -652,15 +769,21 @@ DEV_INLINE void attn_bwd_dkv_tile(const BlockCtx& c, char* smem,
   // lse (to log2 space) and delta of each Q tile travel one tile ahead,
   // next to the tile itself
   const long long row0 = c.bh * T + i0 * KVB;
-  RowPipe rows(lse + row0, delta + row0, lds_lse, lds_dlt, LOG2E, c.tid);
+  RowPipe<TAIL> rows(lse + row0, delta + row0, lds_lse, lds_dlt, LOG2E, c.tid,
+                     T - i0 * KVB);
   pipe.prime();
   rows.fetch();
-  for (int i = i0; i < T / KVB; ++i) {
-    pipe.next(lds_q, lds_do, i + 1 < T / KVB, rows);
+  // Q tiles in all (a name for what the loop reads per iteration)
+  auto n_q = [&]() { return TAIL ? (T + KVB - 1) / KVB : T / KVB; };
+  for (int i = i0; i < n_q(); ++i) {
+    pipe.next(lds_q, lds_do, i + 1 < n_q(), rows);
     __syncthreads();
 
     const int q0 = i * KVB;
     if (q0 + KVB - 1 < key_lo) continue;
+    if constexpr (TAIL) {
+      if (key_lo >= T) continue;   // a wave of padded keys only
+    }
 
     const bool diag = q0 < key_lo + 32;
     const int mask_lo = key_me - q0 - 4 * c.h32;  // diagonal tiles only
@@ -745,8 +868,10 @@ DEV_INLINE void attn_bwd_dkv_tile(const BlockCtx& c, char* smem,
   const long long doff = c.base(sd, H) + (long long)(key_lo) * sd.t;
   bf16* dkp = dk + doff;
   bf16* dvp = dv + doff;
-  store_ctiles(dkp, sd.t, c, dk_acc, [&](int) { return scale; }, stage);
-  store_ctiles(dvp, sd.t, c, dv_acc, [&](int) { return 1.0f; }, stage);
+  store_ctiles<TAIL>(dkp, sd.t, c, dk_acc, [&](int) { return scale; }, stage,
+                     T - key_lo);
+  store_ctiles<TAIL>(dvp, sd.t, c, dv_acc, [&](int) { return 1.0f; }, stage,
+                     T - key_lo);
 }
 
 template <int NW, bool DROP = false>
@@ -768,8 +893,26 @@ __global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
   char smem[attn_lds_bytes(NW) + 2 * KVB * 4];   // + lse and delta of a tile
   BlockCtx c(T / (NW * 32), balance, false);
   do {
-    attn_bwd_dkv_tile<NW, DROP>(c, smem, q, k, v, dout, lse, delta, dk, dv, T,
-                                H, scale, sq, so, sd, drop);
+    attn_bwd_dkv_tile<NW, DROP, false>(c, smem, q, k, v, dout, lse, delta, dk,
+                                       dv, T, H, scale, sq, so, sd, drop);
+  } while (c.next_pass());
+}
+
+template <int NW, bool DROP = false>
+__launch_bounds__(NW * WAVE)
+TAIL_TARGET
+__global__ void attn_bwd_dkv_tail_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k,
+    const bf16* __restrict__ v, const bf16* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    bf16* __restrict__ dk, bf16* __restrict__ dv, int T, int H, float scale,
+    GStride sq, GStride so, GStride sd, Dropout drop, int balance) {
+  __shared__ __attribute__((aligned(16)))
+  char smem[attn_lds_bytes(NW) + 2 * KVB * 4];
+  BlockCtx c((T + NW * 32 - 1) / (NW * 32), balance, false);
+  do {
+    attn_bwd_dkv_tile<NW, DROP, true>(c, smem, q, k, v, dout, lse, delta, dk,
+                                      dv, T, H, scale, sq, so, sd, drop);
   } while (c.next_pass());
 }
 
@@ -777,7 +920,7 @@ __global__ void attn_bwd_dkv_kernel(const bf16* __restrict__ q,
 // Backward dQ: one workgroup per (NW*32)-row Q block; wave w owns 32 rows.
 // ---------------------------------------------------------------------------
 // One Q block (c.tile) of dQ, called once per pass.
-template <int NW, bool DROP>
+template <int NW, bool DROP, bool TAIL>
 DEV_INLINE void attn_bwd_dq_tile(const BlockCtx& c, char* smem,
                                  const bf16* __restrict__ q,
                                  const bf16* __restrict__ k,
@@ -800,7 +943,10 @@ DEV_INLINE void attn_bwd_dq_tile(const BlockCtx& c, char* smem,
   const long long ooff = c.base(so, H) + (long long)(c.tile * BM) * so.t;
   const bf16* qp = q + boff + (long long)(c.tile * BM) * sq.t;
 
-  TilePipe<NT> pipe(k + boff, sq.t, v + boff, sq.t, c.tid);
+  // TAIL: this lane's row exists
+  const bool row_ok = !TAIL || c.tile * BM + c.w * 32 + c.x32 < T;
+
+  TilePipe<NT, TAIL> pipe(k + boff, sq.t, v + boff, sq.t, c.tid, T);
   const FragOff fo(c);
   int f_off[2][4];   // kept in registers here: this kernel has them to spare
 #pragma unroll
@@ -813,16 +959,19 @@ DEV_INLINE void attn_bwd_dq_tile(const BlockCtx& c, char* smem,
   bfrag q_frag[4], do_frag[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    q_frag[s] = load_frag_scaled(qp, c.w * 32 + c.x32, s * 16 + 8 * c.h32,
-                                 sq.t, qscale);
-    do_frag[s] = load_frag(dout + ooff, c.w * 32 + c.x32, s * 16 + 8 * c.h32,
-                           so.t);
+    q_frag[s] = load_frag_scaled<TAIL>(qp, c.w * 32 + c.x32,
+                                       s * 16 + 8 * c.h32, sq.t, qscale,
+                                       row_ok);
+    do_frag[s] = load_frag<TAIL>(dout + ooff, c.w * 32 + c.x32,
+                                 s * 16 + 8 * c.h32, so.t, row_ok);
   }
   const int row_lo = c.tile * BM + c.w * 32;
   const int row_me = row_lo + c.x32;
   const unsigned long long drop_base =
       DROP ? ((unsigned long long)c.bh * T + row_me) * T : 0;
-  const float lse2_me = lse[c.bh * T + row_me] * LOG2E;
+  // a padded row: lse = +inf, so that P = exp2(s - inf) is exactly 0
+  float lse2_me = INFINITY;
+  if (row_ok) lse2_me = lse[c.bh * T + row_me] * LOG2E;
   // delta = rowsum(dO*O) computed here from the fragments already in
   // registers (+ one O load) and PUBLISHED for the dkv kernel, which is
   // launched after this one — replaces a separate full-pass delta kernel.
@@ -830,7 +979,8 @@ DEV_INLINE void attn_bwd_dq_tile(const BlockCtx& c, char* smem,
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     union { bfrag f; short8v v8; } ov;
-    ov.f = load_frag(o + ooff, c.w * 32 + c.x32, s * 16 + 8 * c.h32, so.t);
+    ov.f = load_frag<TAIL>(o + ooff, c.w * 32 + c.x32, s * 16 + 8 * c.h32,
+                           so.t, row_ok);
     union { bfrag f; short8v v8; } dv;
     dv.f = do_frag[s];
 #pragma unroll
@@ -838,7 +988,7 @@ DEV_INLINE void attn_bwd_dq_tile(const BlockCtx& c, char* smem,
       dlt_me += bf_elem(ov.v8, e) * bf_elem(dv.v8, e);
   }
   dlt_me += __shfl_xor(dlt_me, 32, WAVE);
-  if (c.lane < 32) delta[c.bh * T + row_me] = dlt_me;
+  if (c.lane < 32 && row_ok) delta[c.bh * T + row_me] = dlt_me;
 
   const f32x16 kzero = {};
   f32x16 dq_acc[2] = {};
@@ -851,6 +1001,9 @@ DEV_INLINE void attn_bwd_dq_tile(const BlockCtx& c, char* smem,
 
     const int key0 = j * KVB;
     if (key0 > row_lo + 31) continue;
+    if constexpr (TAIL) {
+      if (row_lo >= T) continue;   // a wave of padded rows only
+    }
 
     const bool diag = key0 + KVB - 1 > row_lo;
     PackedC dS;
@@ -909,8 +1062,8 @@ DEV_INLINE void attn_bwd_dq_tile(const BlockCtx& c, char* smem,
     __builtin_amdgcn_s_setprio(0);
   }
 
-  store_ctiles(dq + c.base(sd, H) + (long long)row_lo * sd.t, sd.t, c, dq_acc,
-               [&](int) { return scale; }, stage);
+  store_ctiles<TAIL>(dq + c.base(sd, H) + (long long)row_lo * sd.t, sd.t, c,
+                     dq_acc, [&](int) { return scale; }, stage, T - row_lo);
 }
 
 template <int NW, bool DROP = false>
@@ -928,8 +1081,26 @@ __global__ void attn_bwd_dq_kernel(const bf16* __restrict__ q,
   __shared__ __attribute__((aligned(16))) char smem[attn_lds_bytes(NW)];
   BlockCtx c(T / (NW * 32), balance, true);
   do {
-    attn_bwd_dq_tile<NW, DROP>(c, smem, q, k, v, o, dout, lse, delta, dq, T, H,
-                               scale, sq, so, sd, drop);
+    attn_bwd_dq_tile<NW, DROP, false>(c, smem, q, k, v, o, dout, lse, delta,
+                                      dq, T, H, scale, sq, so, sd, drop);
+  } while (c.next_pass());
+}
+
+template <int NW, bool DROP = false>
+__launch_bounds__(NW * WAVE)
+TAIL_TARGET
+__global__ void attn_bwd_dq_tail_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k,
+    const bf16* __restrict__ v, const bf16* __restrict__ o,
+    const bf16* __restrict__ dout, const float* __restrict__ lse,
+    float* __restrict__ delta, bf16* __restrict__ dq, int T, int H,
+    float scale, GStride sq, GStride so, GStride sd, Dropout drop,
+    int balance) {
+  __shared__ __attribute__((aligned(16))) char smem[attn_lds_bytes(NW)];
+  BlockCtx c((T + NW * 32 - 1) / (NW * 32), balance, true);
+  do {
+    attn_bwd_dq_tile<NW, DROP, true>(c, smem, q, k, v, o, dout, lse, delta, dq,
+                                     T, H, scale, sq, so, sd, drop);
   } while (c.next_pass());
 }
 
@@ -948,23 +1119,43 @@ static Dropout make_dropout(float p, unsigned long long seed) {
   return {seed, keep_thr, (float)(1.0 / keepd)};
 }
 
-// Calls f(NW, DROP) as std::integral_constants. NW is the widest block that
-// divides T, capped by the knob `nw_env` (2, 4 or 8, anything else counts as
-// the default 8; read at every launch — within-box A/B, because box-to-box
-// wall-clock noise is ~3%). 8-wave blocks are the measured best: backward
-// 285us vs 332us for 4-wave at B8/H16/T1024 (pre-tr16), staging
-// amortization across 8 waves beat block overlap.
+// Calls f(NW, DROP, TAIL) as std::integral_constants. TAIL: T % 64 != 0.
+// NW is the widest block that divides T rounded up to 64, capped by the knob
+// `nw_env` (2, 4 or 8, anything else counts as the default 8; read at every
+// launch — within-box A/B, because box-to-box wall-clock noise is ~3%).
+// 8-wave blocks are the measured best: backward 285us vs 332us for 4-wave at
+// B8/H16/T1024 (pre-tr16), staging amortization across 8 waves beat block
+// overlap.
 template <typename F>
 static void attn_dispatch(int T, const char* nw_env, bool drop, F f) {
   const long long knob = env_int(nw_env, 8);
   const int nw_max = (knob == 2 || knob == 4) ? (int)knob : 8;
-  auto with_nw = [&](auto DROP) {
-    if (T % 256 == 0 && nw_max == 8) f(std::integral_constant<int, 8>{}, DROP);
-    else if (T % 128 == 0 && nw_max >= 4) f(std::integral_constant<int, 4>{}, DROP);
-    else f(std::integral_constant<int, 2>{}, DROP);
+  const int T64 = (T + KVB - 1) / KVB * KVB;
+  auto with_nw = [&](auto DROP, auto TAIL) {
+    if (T64 % 256 == 0 && nw_max == 8)
+      f(std::integral_constant<int, 8>{}, DROP, TAIL);
+    else if (T64 % 128 == 0 && nw_max >= 4)
+      f(std::integral_constant<int, 4>{}, DROP, TAIL);
+    else
+      f(std::integral_constant<int, 2>{}, DROP, TAIL);
   };
-  if (drop) with_nw(std::true_type{}); else with_nw(std::false_type{});
+  auto with_drop = [&](auto TAIL) {
+    if (drop) with_nw(std::true_type{}, TAIL);
+    else with_nw(std::false_type{}, TAIL);
+  };
+  if (T % KVB) with_drop(std::true_type{}); else with_drop(std::false_type{});
 }
+
+// The three kernels of one (NW, DROP, TAIL).
+template <int NW, bool DROP, bool TAIL>
+struct AttnKernels {
+  static constexpr auto fwd =
+      TAIL ? attn_fwd_tail_kernel<NW, DROP> : attn_fwd_kernel<NW, DROP>;
+  static constexpr auto dq =
+      TAIL ? attn_bwd_dq_tail_kernel<NW, DROP> : attn_bwd_dq_kernel<NW, DROP>;
+  static constexpr auto dkv = TAIL ? attn_bwd_dkv_tail_kernel<NW, DROP>
+                                   : attn_bwd_dkv_kernel<NW, DROP>;
+};
 
 // Workgroups of `Kernel` that the device holds at once (CUs x resident
 // blocks per CU, as the runtime computes it from the kernel's registers and
@@ -1029,13 +1220,16 @@ hipError_t tdsa_attn_fwd(const void* q, const void* k, const void* v, void* o,
                          float scale, const long long* sq_in,
                          const long long* so_in, float dropout_p,
                          unsigned long long seed, hipStream_t stream) {
-  if (T % KVB) return hipErrorInvalidValue;
+  if (T < 1) return hipErrorInvalidValue;
   const GStride sq = gstride(sq_in), so = gstride(so_in);
   const Dropout drop = make_dropout(dropout_p, seed);
-  attn_dispatch(T, "TDSA_ATTN_FWD_NW", dropout_p > 0.0f, [&](auto nw, auto dr) {
+  attn_dispatch(T, "TDSA_ATTN_FWD_NW", dropout_p > 0.0f,
+                [&](auto nw, auto dr, auto tl) {
     constexpr int NW = decltype(nw)::value;
-    constexpr auto fwd = attn_fwd_kernel<NW, decltype(dr)::value>;
-    const TileMap m = tile_map<fwd>(T / (NW * 32), B * H, NW * WAVE);
+    constexpr auto fwd =
+        AttnKernels<NW, decltype(dr)::value, decltype(tl)::value>::fwd;
+    const int n_tiles = (T + NW * 32 - 1) / (NW * 32);
+    const TileMap m = tile_map<fwd>(n_tiles, B * H, NW * WAVE);
     hipLaunchKernelGGL(fwd, m.grid, dim3(NW * WAVE), 0, stream,
                        (const bf16*)q, (const bf16*)k, (const bf16*)v,
                        (bf16*)o, lse, T, (int)H, scale, sq, so, drop,
@@ -1051,20 +1245,22 @@ hipError_t tdsa_attn_bwd(const void* q, const void* k, const void* v,
                          const long long* sq_in, const long long* so_in,
                          const long long* sd_in, float dropout_p,
                          unsigned long long seed, hipStream_t stream) {
-  if (T % KVB) return hipErrorInvalidValue;
+  if (T < 1) return hipErrorInvalidValue;
   const GStride sq = gstride(sq_in), so = gstride(so_in), sd = gstride(sd_in);
   const Dropout drop = make_dropout(dropout_p, seed);
   // dq runs FIRST: it computes and publishes delta = rowsum(dO*O) from
   // fragments it loads anyway; dkv (same stream) consumes it.
-  attn_dispatch(T, "TDSA_ATTN_BWD_NW", dropout_p > 0.0f, [&](auto nw, auto dr) {
+  attn_dispatch(T, "TDSA_ATTN_BWD_NW", dropout_p > 0.0f,
+                [&](auto nw, auto dr, auto tl) {
     constexpr int NW = decltype(nw)::value;
-    constexpr bool DROP = decltype(dr)::value;
-    constexpr auto dq_k = attn_bwd_dq_kernel<NW, DROP>;
-    constexpr auto dkv_k = attn_bwd_dkv_kernel<NW, DROP>;
+    using K = AttnKernels<NW, decltype(dr)::value, decltype(tl)::value>;
+    constexpr auto dq_k = K::dq;
+    constexpr auto dkv_k = K::dkv;
     const dim3 block(NW * WAVE);
+    const int n_tiles = (T + NW * 32 - 1) / (NW * 32);
     // the two kernels differ in residency, so each gets its own mapping
-    const TileMap mq = tile_map<dq_k>(T / (NW * 32), B * H, NW * WAVE);
-    const TileMap mkv = tile_map<dkv_k>(T / (NW * 32), B * H, NW * WAVE);
+    const TileMap mq = tile_map<dq_k>(n_tiles, B * H, NW * WAVE);
+    const TileMap mkv = tile_map<dkv_k>(n_tiles, B * H, NW * WAVE);
     hipLaunchKernelGGL(dq_k, mq.grid, block, 0, stream,
                        (const bf16*)q, (const bf16*)k, (const bf16*)v,
                        (const bf16*)o, (const bf16*)dout, lse, delta,

@@ -107,7 +107,10 @@ hipError_t tdsa_grad_sumsq_multi(const void* blob, int ndescs, int nchunks,
                                  hipStream_t stream);
 
 // ---- attention.hip ----------------------------------------------------------
-// bf16 (B, H, T, 64) tensors with T % 64 == 0 and a contiguous last dim.
+// bf16 (B, H, T, 64) tensors with any T >= 1 and a contiguous last dim.
+// T % 64 == 0 runs the aligned kernels, any other T their tail variants,
+// which read and write no row >= T of a (batch, head) and nothing past
+// index B*H*T - 1 of lse and delta.
 // sq, so, sd: {b, h, t} strides in elements of q/k/v, of o/dout and of
 // dq/dk/dv. lse fp32 [B, H, T] contiguous. dropout_p > 0 applies the mask
 // that `seed` generates, the same in forward and backward.

@@ -97,6 +97,18 @@ struct Stage {
     for (int rep = 0; rep < REPS; ++rep) buf[rep] = load8(src[rep]);
   }
 
+  // fetch() of a tile that has only its first `rows` rows (any value; <= 0:
+  // none): one compare per 16-byte chunk, a chunk of a later row is not read
+  // and arrives as zeros. `tid` is the one given to init().
+  DEV_INLINE void fetch_rows(short8v (&buf)[REPS], int tid, int rows) {
+#pragma unroll
+    for (int rep = 0; rep < REPS; ++rep) {
+      short8v v = {};
+      if (((tid + rep * NT) >> 3) < rows) v = load8(src[rep]);
+      buf[rep] = v;
+    }
+  }
+
   DEV_INLINE void put(char* lds, const short8v (&buf)[REPS]) {
 #pragma unroll
     for (int rep = 0; rep < REPS; ++rep)

@@ -1,23 +1,28 @@
 """Isolated attention kernel benchmark (fwd / bwd), with TF/s accounting.
 
 Usage (GPU box): python scripts/bench_attn.py [--T 1024] [--B 8] [--H 16]
-Causal flops: ~0.5 * 2 gemms * 2*B*H*T^2*D each for fwd; bwd ~2.5x fwd.
+Any T: a length that is no multiple of 64 runs the ragged entry points (the
+tail kernels). Causal flops: ~0.5 * 2 gemms * 2*B*H*T^2*D each for fwd; bwd
+~2.5x fwd.
+
+    --tree DIR     import the package from another checkout (A/B runs of two
+                   builds in one session, alternating)
+    --composite    also time ops.attention._composite_fwd/_bwd, the path that
+                   ragged T took before the tail kernels (fp32 (B,H,T,T)
+                   scores: pick a --B that fits)
+    --sdpa         also time torch's scaled_dot_product_attention forward
 """
 
 import argparse
+import importlib
 import math
 import os
 import sys
 import time
 
-sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
-
-import torch
-
-from tiny_deepspeed_amd import _C
-
 
 def timeit(fn, iters=20, warmup=5):
+    import torch
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
@@ -34,35 +39,57 @@ def main():
     p.add_argument("--H", type=int, default=16)
     p.add_argument("--T", type=int, default=1024)
     p.add_argument("--iters", type=int, default=20)
+    p.add_argument("--tree", default=os.path.join(os.path.dirname(__file__), ".."))
+    p.add_argument("--composite", action="store_true")
+    p.add_argument("--sdpa", action="store_true")
     args = p.parse_args()
+    sys.path.insert(0, os.path.abspath(args.tree))
+    import torch
+    _C = importlib.import_module("tiny_deepspeed_amd._C")
+
     B, H, T, D = args.B, args.H, args.T, 64
+    fwd, bwd = _C.attention_fwd, _C.attention_bwd
+    if T % 64:
+        fwd, bwd = _C.attention_ragged_fwd, _C.attention_ragged_bwd
     scale = 1.0 / math.sqrt(D)
     torch.manual_seed(0)
     q = torch.randn(B, H, T, D, device="cuda", dtype=torch.bfloat16)
     k = torch.randn_like(q)
     v = torch.randn_like(q)
-    o, lse = _C.attention_fwd(q, k, v, scale)
+    o, lse = fwd(q, k, v, scale)
     do = torch.randn_like(o)
 
-    t_fwd = timeit(lambda: _C.attention_fwd(q, k, v, scale), args.iters)
-    t_bwd = timeit(lambda: _C.attention_bwd(q, k, v, o, lse, do, scale),
-                   args.iters)
+    t_fwd = timeit(lambda: fwd(q, k, v, scale), args.iters)
+    t_bwd = timeit(lambda: bwd(q, k, v, o, lse, do, scale), args.iters)
     # causal effective flops
     f_fwd = 0.5 * 2 * (2 * B * H * T * T * D)
     f_bwd = 0.5 * 5 * (2 * B * H * T * T * D)  # dkv recompute S,dP + dV,dK; dq S,dP,dQ
-    print(f"fwd: {t_fwd*1e6:8.1f} us  {f_fwd/t_fwd/1e12:7.1f} TF/s (causal-effective)")
-    print(f"bwd: {t_bwd*1e6:8.1f} us  {f_bwd/t_bwd/1e12:7.1f} TF/s (causal-effective)")
+    tag = f"B{B} H{H} T{T}"
+    print(f"{tag} fwd: {t_fwd*1e6:8.1f} us  {f_fwd/t_fwd/1e12:7.1f} TF/s (causal-effective)")
+    print(f"{tag} bwd: {t_bwd*1e6:8.1f} us  {f_bwd/t_bwd/1e12:7.1f} TF/s (causal-effective)")
 
-    # sdpa comparison (rocm flash attention via torch, if available)
-    qf = q.clone(); kf = k.clone(); vf = v.clone()
-    def sdpa():
-        return torch.nn.functional.scaled_dot_product_attention(
-            qf, kf, vf, is_causal=True, scale=scale)
-    try:
-        t_sdpa = timeit(sdpa, args.iters)
-        print(f"torch sdpa fwd: {t_sdpa*1e6:8.1f} us  {f_fwd/t_sdpa/1e12:7.1f} TF/s")
-    except Exception as e:
-        print("sdpa failed:", e)
+    if args.composite:
+        att = importlib.import_module("tiny_deepspeed_amd.ops.attention")
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        iters = max(3, args.iters // 20)
+        t_cf = timeit(lambda: att._composite_fwd(q, k, v, scale), iters, 2)
+        t_cb = timeit(lambda: att._composite_bwd(q, k, v, o, lse, do, scale),
+                      iters, 2)
+        peak = (torch.cuda.max_memory_allocated() - base) / 2**20
+        print(f"{tag} composite fwd: {t_cf*1e6:8.1f} us  bwd: {t_cb*1e6:8.1f} us  "
+              f"peak extra memory {peak:.0f} MiB")
+
+    if args.sdpa:
+        # rocm flash attention via torch, if available
+        def sdpa():
+            return torch.nn.functional.scaled_dot_product_attention(
+                q, k, v, is_causal=True, scale=scale)
+        try:
+            t_sdpa = timeit(sdpa, args.iters)
+            print(f"{tag} torch sdpa fwd: {t_sdpa*1e6:8.1f} us  {f_fwd/t_sdpa/1e12:7.1f} TF/s")
+        except Exception as e:
+            print("sdpa failed:", e)
 
 
 if __name__ == "__main__":
