@@ -130,10 +130,12 @@ hipError_t tdsa_attn_bwd(const void* q, const void* k, const void* v,
 
 // ---- gemm_tn.hip ------------------------------------------------------------
 // Split count for dw = dy[M, N]^T x[M, K]; <= 0 means the shape is not taken
-// (needs M % 64 == 0, N % 128 == 0, K % 128 == 0).
+// (needs M >= 1, N % 64 == 0, K % 64 == 0; a shape with M % 64, N % 128 or
+// K % 128 nonzero runs the EDGE instantiations, always 4 waves).
 int tdsa_gemm_tn_splits(long long M, int N, int K);
-// dy, x bf16; dw fp32 [splits, N, K], one slab per split (need not be
-// initialised), summed by the caller.
+// dy, x bf16, contiguous [M, N] and [M, K], same contract; no row >= M is
+// read. dw fp32 [splits, N, K], one slab per split (need not be initialised),
+// summed by the caller.
 hipError_t tdsa_gemm_tn(const void* dy, const void* x, float* dw, long long M,
                         int N, int K, hipStream_t stream);
 

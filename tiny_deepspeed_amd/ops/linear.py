@@ -18,7 +18,9 @@ MI355X design note: the forward NT GEMM stays on the library path —
 measured at the practical MFMA ceiling (profiles/gemm_shapes_hipblaslt.txt,
 fwd NT 1436 TF/s) — while dW (TN, the weakest library shape) carries a
 hand-written split-M MFMA kernel as a tuner candidate so the question is
-settled by measurement per shape, not by assertion. dX as an NN GEMM gets
+settled by measurement per shape, not by assertion; the kernel takes any
+M = B*T and widths that are multiples of 64 (edge tiles and a ragged last
+chunk are its EDGE instantiations). dX as an NN GEMM gets
 the library's smaller tiles; with W^T made row-major first (one native
 transpose per call, never cached, so no strategy can see a stale copy) it is
 the forward's layout again, and the tuner times both per shape, transpose
@@ -106,15 +108,17 @@ def _dw_hip_supported(dy2, x2):
         return False
     if not _ext.ext_available() or not hasattr(_ext.get_ext(), "gemm_tn"):
         return False
-    # kernel contract (csrc/kernels/gemm_tn.hip): bf16, M % 64 == 0,
-    # N/K % 128 == 0 — covers the GPT-2 small/medium/large GEMM families
-    # (xl's 1600-wide shapes fall to the library candidate)
+    # kernel contract (csrc/kernels/gemm_tn.hip): bf16, any M >= 1,
+    # N/K % 64 == 0 — every GPT-2 preset's widths (xl's 1600/4800/6400
+    # included) at any batch * sequence length
     return (
         dy2.dtype == torch.bfloat16
         and x2.dtype == torch.bfloat16
-        and dy2.shape[0] % 64 == 0
-        and dy2.shape[1] % 128 == 0
-        and x2.shape[1] % 128 == 0
+        and dy2.shape[0] >= 1
+        and dy2.shape[1] >= 64
+        and x2.shape[1] >= 64
+        and dy2.shape[1] % 64 == 0
+        and x2.shape[1] % 64 == 0
     )
 
 
