@@ -535,14 +535,15 @@ at::Tensor linear_dx_nt(at::Tensor dy2, at::Tensor w) {
 // q's extents and, per group, one tensor's strides (`lead`: q for q/k/v, o for
 // o/dout, dq for dq/dk/dv), so any other shape or stride stops here.
 // ragged: the attention_ragged_* entry points, any T >= 1.
+// D: the entry point's head dim (64; 128 for attention_d128_*).
 struct AttnTensor { const char* name; const at::Tensor &t, &lead; };
 static void check_attn_call(std::initializer_list<AttnTensor> tensors,
-                            double dropout_p, bool ragged) {
+                            double dropout_p, bool ragged, int64_t D = 64) {
   const at::Tensor& q = tensors.begin()->t;
   for (const auto& [name, t, lead] : tensors) {
     TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-    TORCH_CHECK(t.dim() == 4 && t.size(3) == 64, name,
-                ": attention kernel requires (B,H,T,64)");
+    TORCH_CHECK(t.dim() == 4 && t.size(3) == D, name,
+                ": attention kernel requires (B,H,T,", D, ")");
     TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
     TORCH_CHECK(t.stride(3) == 1, name, " last dim must be contiguous");
     TORCH_CHECK(t.sizes() == q.sizes(), name, " must have q's sizes ",
@@ -645,6 +646,50 @@ std::vector<at::Tensor> attention_ragged_bwd(
                        scale, dq_out, dk_out, dv_out, dropout_p, seed);
 }
 
+// Head dim 128: aligned T, no dropout (csrc/kernels/attention_d128.hip).
+std::vector<at::Tensor> attention_d128_fwd(at::Tensor q, at::Tensor k,
+                                           at::Tensor v, double scale,
+                                           c10::optional<at::Tensor> out) {
+  at::Tensor o = out.has_value() ? *out : at::empty_like(q);
+  check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"out", o, o}}, 0.0,
+                  false, 128);
+  const long long B = q.size(0), H = q.size(1), T = q.size(2);
+  auto lse = at::empty({B, H, T}, q.options().dtype(at::kFloat));
+  check_hip(tdsa_attn_d128_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                               o.data_ptr(), lse.data_ptr<float>(), B, H,
+                               (int)T, (float)scale, strides3(q).data(),
+                               strides3(o).data(), cur_stream()),
+            "attention_d128_fwd");
+  return {o, lse};
+}
+
+std::vector<at::Tensor> attention_d128_bwd(
+    at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
+    at::Tensor dout, double scale, c10::optional<at::Tensor> dq_out,
+    c10::optional<at::Tensor> dk_out, c10::optional<at::Tensor> dv_out) {
+  at::Tensor dq = dq_out.has_value() ? *dq_out : at::empty_like(q);
+  at::Tensor dk = dk_out.has_value() ? *dk_out : at::empty_like(k);
+  at::Tensor dv = dv_out.has_value() ? *dv_out : at::empty_like(v);
+  check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"o", o, o},
+                   {"dout", dout, o}, {"dq", dq, dq}, {"dk", dk, dq},
+                   {"dv", dv, dq}}, 0.0, false, 128);
+  const long long B = q.size(0), H = q.size(1), T = q.size(2);
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
+                  lse.numel() == B * H * T,
+              "lse must be fp32 on GPU with B*H*T elements, got ", lse.sizes());
+  auto lsec = lse.contiguous();
+  auto delta = at::empty({B * H * T}, q.options().dtype(at::kFloat));
+  check_hip(tdsa_attn_d128_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                               o.data_ptr(), lsec.data_ptr<float>(),
+                               dout.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                               dv.data_ptr(), delta.data_ptr<float>(), B, H,
+                               (int)T, (float)scale, strides3(q).data(),
+                               strides3(o).data(), strides3(dq).data(),
+                               cur_stream()),
+            "attention_d128_bwd");
+  return {dq, dk, dv};
+}
+
 // ---- debug probes ---------------------------------------------------------
 at::Tensor dbg_mfma(at::Tensor A, at::Tensor B, int64_t variant) {
   check_call("dbg_mfma", {{"A", A, at::kBFloat16, 16 * 32},
@@ -731,6 +776,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("scale"), py::arg("dq") = py::none(),
           py::arg("dk") = py::none(), py::arg("dv") = py::none(),
           py::arg("dropout_p") = 0.0, py::arg("seed") = 0);
+  mod.def("attention_d128_fwd", &attention_d128_fwd, py::arg("q"),
+          py::arg("k"), py::arg("v"), py::arg("scale"),
+          py::arg("out") = py::none());
+  mod.def("attention_d128_bwd", &attention_d128_bwd, py::arg("q"),
+          py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"),
+          py::arg("dout"), py::arg("scale"), py::arg("dq") = py::none(),
+          py::arg("dk") = py::none(), py::arg("dv") = py::none());
   mod.def("attention_ragged_fwd", &attention_ragged_fwd, py::arg("q"),
           py::arg("k"), py::arg("v"), py::arg("scale"),
           py::arg("out") = py::none(), py::arg("dropout_p") = 0.0,

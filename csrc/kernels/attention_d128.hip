@@ -1,0 +1,699 @@
+// Fused causal attention for head dim 128 (bf16, T % 64 == 0, no dropout).
+//
+// Same scheme and number formats as attention.hip (head dim 64): forward with
+// online softmax in exp2 space and a natural-log lse; backward in two kernels
+// without atomics, dq first (it publishes delta = rowsum(dO*O)), then dk/dv.
+// The three conventions are kept, so the same error model holds: swapped
+// S^T = mfma(K, Q) (a softmax row lives in one lane pair), P and dS from C
+// layout to A fragments through v_permlane32_swap, Q (K in dk/dv) prescaled by
+// scale*log2e and rounded to bf16. scale is 2^-3.5 here: the prescale is NOT
+// exact, which the error model already covers (it rounds q*scale*log2e).
+// The skeleton (BlockCtx, tile_map, TilePipe, RowPipe, FragOff, PackedC) is
+// attn_common.h, shared with attention.hip.
+//
+// Operand tiles: a 64-row K, V, Q or dO tile is 64 x 128 bf16 = TWO swizzled
+// [64][64] images of mfma.h side by side in LDS (columns 0-63, then 64-127,
+// IMG bytes apart). One TilePipe stages the two images of one tensor: its
+// "pair" is (left half, right half) of the same 64 rows. A fragment or a
+// transpose read of d-slice s / column tile dt picks the image by s >> 2 /
+// dt >> 1 and uses the unchanged [64][64] offsets inside it.
+//
+// Geometry: what does not carry over from head dim 64 is the register budget.
+// A wave keeps 32 rows as before, and per wave the live state is
+//   fwd : O 64 fp32 + Q fragments 32 + S^T 32 + staging
+//   dq  : dQ 64 + Q, dO fragments 64 + S^T, dP^T 32 + dS 16 + staging
+//   dkv : dK, dV 128 + K, V fragments 64 + S, dP 32 + P, dS 32 + staging
+// An 8-wave block (2 waves per SIMD) caps a lane at 256 registers, which dkv
+// exceeds before staging. So every kernel here runs 4-WAVE blocks (128 rows;
+// 2-wave blocks where T % 128 != 0): one wave per SIMD and block, up to 512
+// registers with the AGPR half, K and V (Q, dO) fragments stay pinned in
+// registers and the staging cost of a tile is shared by 4 waves instead of 8.
+// The price is occupancy: a CU holds as many blocks as 512 / registers allows
+// (docs/kernels.md, "Head dim 128" has the counts); dkv is left with one wave
+// per SIMD and hides its softmax behind nothing but its own MFMA queue.
+//
+// MFMA per 64-row tile and wave: fwd 16 (S^T: 8 d-slices x 2 key halves) + 16
+// (O: 4 key slices x 4 column tiles); dq 32 + 16; dkv 32 + 32.
+//
+// LDS: two 64 x 128 tiles (32 KB) per block, plus lse/delta of a Q tile in
+// dkv. The epilogue images (one [32][128] bf16 image per wave, whole 256-byte
+// rows out) reuse the tile space after a block barrier: every wave of a block
+// runs the same number of loop iterations, so the barrier costs no waiting
+// that the loop's own barriers had not already imposed.
+#include "common.h"
+#include "launchers.h"
+#include "attn_common.h"
+#include "mfma.h"
+
+#include <type_traits>
+
+namespace tdsa {
+
+// The kernels are compiled without packed fp32 math, the project's choice for
+// attention kernels since the tail kernels of attention.hip, whose packed
+// build measured slower (profiles/attn_ragged.txt: fwd 139 against 127 us).
+// A packed build of these kernels has not been measured.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define NO_PK_F32
+#endif
+
+constexpr int IMG = KVB * 64 * 2;    // bytes of one swizzled [64][64] image
+constexpr int TILE128 = 2 * IMG;     // a 64 x 128 tile: two images
+constexpr int STAGE128 = 32 * 128 * 2;   // a wave's [32][128] epilogue image
+constexpr int HALF = 64;             // elements from a row's left to right half
+
+// Stages one tensor's 64 x 128 tiles: image 0 <- columns 0-63, 1 <- 64-127.
+template <int NT>
+DEV_INLINE TilePipe<NT> tile128_pipe(const bf16* g, int st, int tid) {
+  return TilePipe<NT>(g, st, g + HALF, st, tid);
+}
+
+// TilePipe::next for the two tensors of a loop at once, under ONE barrier
+// (each pipe's own next() would bring its own): barrier (the previous tiles
+// are consumed), pending registers -> LDS, and with `more` the loads of the
+// following tiles. `rows` rides along as in TilePipe::next. The caller places
+// the barrier that publishes the tiles.
+template <int NT, typename Rows = typename TilePipe<NT>::NoRows>
+DEV_INLINE void next_tiles128(TilePipe<NT>& x, char* lds_x, TilePipe<NT>& y,
+                              char* lds_y, bool more, Rows&& rows = Rows{}) {
+  __syncthreads();
+  x.a.put(lds_x, x.pend_a);
+  x.b.put(lds_x + IMG, x.pend_b);
+  y.a.put(lds_y, y.pend_a);
+  y.b.put(lds_y + IMG, y.pend_b);
+  rows.put();
+  if (more) {
+    x.a.advance();
+    x.b.advance();
+    y.a.advance();
+    y.b.advance();
+    x.fetch();
+    y.fetch();
+    rows.advance();
+    rows.fetch();
+  }
+}
+
+// Pinned B operands of one row: d-slices 0..7, optionally prescaled.
+DEV_INLINE void load_row_frags(bfrag (&f)[8], const bf16* p, int row, int h32,
+                               int st) {
+#pragma unroll
+  for (int s = 0; s < 8; ++s) f[s] = load_frag(p, row, s * 16 + 8 * h32, st);
+}
+
+DEV_INLINE void load_row_frags_scaled(bfrag (&f)[8], const bf16* p, int row,
+                                      int h32, int st, float mul) {
+#pragma unroll
+  for (int s = 0; s < 8; ++s)
+    f[s] = load_frag_scaled(p, row, s * 16 + 8 * h32, st, mul);
+}
+
+// acc = A(32-row half t2 of the tile at `lds`) x B(pinned row fragments),
+// reduced over all 128 columns: 8 MFMA.
+DEV_INLINE f32x16 mfma_rows_d128(const char* lds, const FragOff& fo, int t2,
+                                 const bfrag (&b)[8], const f32x16& zero) {
+  f32x16 acc = MFMA32(lds_read16(lds, fo(t2, 0)), b[0], zero);
+#pragma unroll
+  for (int s = 1; s < 8; ++s)
+    acc = MFMA32(lds_read16(lds + (s >> 2) * IMG, fo(t2, s & 3)), b[s], acc);
+  return acc;
+}
+
+// The same with the B rows read from LDS as well: 32-row half tb of the
+// (prescaled) tile at `lds_b` (the 2-wave dkv kernel, whose staging registers
+// leave no room for pinned fragments).
+DEV_INLINE f32x16 mfma_rows_d128(const char* lds, const FragOff& fo, int t2,
+                                 const char* lds_b, int tb,
+                                 const f32x16& zero) {
+  // tb is a run-time value (the wave index): half tb is 32 rows of 128 bytes
+  // past half 0. Indexing FragOff's row[] with it made the compiler move
+  // the struct to LDS (2 KB per block).
+  lds_b += tb * (32 * 128);
+  f32x16 acc = MFMA32(lds_read16(lds, fo(t2, 0)), lds_read16(lds_b, fo(0, 0)),
+                      zero);
+#pragma unroll
+  for (int s = 1; s < 8; ++s)
+    acc = MFMA32(lds_read16(lds + (s >> 2) * IMG, fo(t2, s & 3)),
+                 lds_read16(lds_b + (s >> 2) * IMG, fo(0, s & 3)), acc);
+  return acc;
+}
+
+// One-shot staging of the 64 x 128 tile at g (row stride st) times mul,
+// rounded to bf16, as two swizzled images at lds: 1024 chunks over NT threads.
+template <int NT>
+DEV_INLINE void stage_tile128_scaled(char* lds, const bf16* g, int st, int tid,
+                                     float mul) {
+#pragma unroll
+  for (int rep = 0; rep < 1024 / NT; ++rep) {
+    const int chunk = tid + rep * NT;
+    const int row = chunk >> 4, piece = chunk & 15;
+    const short8v v = load8(g + (long long)row * st + piece * 8);
+    short8v w;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) w[e] = bf_pack(bf_elem(v, e) * mul);
+    *reinterpret_cast<short8v*>(lds + (piece >> 3) * IMG +
+                                swz(row, (piece & 7) * 16)) = w;
+  }
+}
+
+// acc[dt] += A-fragment `a` (k = rows 16s..16s+15 of the tile) x the tile's
+// 32-column tile dt, read transposed: 4 MFMA.
+DEV_INLINE void mfma_cols_d128(f32x16 (&acc)[4], const bfrag& a,
+                               const char* lds, const int (&trb)[2][2], int s) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+    acc[dt] = MFMA32(a, tr_bfrag(lds + (dt >> 1) * IMG,
+                                 trb[dt & 1][0] + s * 2048,
+                                 trb[dt & 1][1] + s * 2048),
+                     acc[dt]);
+}
+
+// Epilogue of one wave's 32 x 128 result (four C tiles): element
+// (crow(r,h32), 32*dt + x32) = acc[dt][r] * mul(r) as bf16, through the
+// wave's own [32][128] LDS image and out as whole 256-byte rows (16 lanes x
+// 16 bytes, 4 rows per store instruction, 8 instructions).
+template <typename F>
+DEV_INLINE void store_ctiles128(bf16* p, int st, const BlockCtx& c,
+                                const f32x16 (&acc)[4], F mul, char* stage) {
+  bf16* img = reinterpret_cast<bf16*>(stage);
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      img[crow(r, c.h32) * 128 + dt * 32 + c.x32] = f2bf(acc[dt][r] * mul(r));
+  wave_lds_fence();
+  const int piece = c.lane & 15;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int row = 4 * i + (c.lane >> 4);
+    store8(p + row * st + piece * 8,
+           *reinterpret_cast<const short8v*>(stage + row * 256 + piece * 16));
+  }
+  wave_lds_fence();   // the image is free for this wave's next result
+}
+
+// Waves per SIMD that the forward and dq kernels are compiled for. 2 holds
+// the 4-wave kernels to 256 registers (left alone the compiler takes 316 and
+// 344 of the 512 a lone wave may have, and a CU then holds one block, not
+// two). The 2-wave kernels stage twice as much per thread and spill under
+// that cap, so they keep the full file (363 and 392).
+constexpr int fwd_dq_waves_per_simd(int nw) { return nw == 4 ? 2 : 1; }
+
+// ---------------------------------------------------------------------------
+// Forward: one workgroup per (NW*32)-row Q block; wave w owns 32 rows.
+// ---------------------------------------------------------------------------
+template <int NW>
+DEV_INLINE void d128_fwd_tile(const BlockCtx& c, char* smem,
+                              const bf16* __restrict__ q,
+                              const bf16* __restrict__ k,
+                              const bf16* __restrict__ v,
+                              bf16* __restrict__ o, float* __restrict__ lse,
+                              int T, int H, float scale, const GStride& sq,
+                              const GStride& so) {
+  constexpr int BM = NW * 32;
+  constexpr int NT = NW * WAVE;
+  char* lds_k = smem;
+  char* lds_v = smem + TILE128;
+
+  const long long boff = c.base(sq, H);
+  const int row_lo = c.tile * BM + c.w * 32;
+  const int row_me = row_lo + c.x32;
+
+  TilePipe<NT> pipe_k = tile128_pipe<NT>(k + boff, sq.t, c.tid);
+  TilePipe<NT> pipe_v = tile128_pipe<NT>(v + boff, sq.t, c.tid);
+  const FragOff kf(c);
+  int trb[2][2];
+  tr_bases(c.lane, trb);
+  bfrag q_frag[8];
+  load_row_frags_scaled(q_frag, q + boff, row_me, c.h32, sq.t, scale * LOG2E);
+
+  const f32x16 kzero = {};
+  f32x16 o_acc[4] = {};
+  float m_run = -INFINITY;
+  float l_run = 0.f;
+
+  const int n_kv = (c.tile + 1) * BM / KVB;
+  pipe_k.prime();
+  pipe_v.prime();
+  for (int j = 0; j < n_kv; ++j) {
+    next_tiles128(pipe_k, lds_k, pipe_v, lds_v, j + 1 < n_kv);
+    __syncthreads();
+
+    const int key0 = j * KVB;
+    if (key0 > row_lo + 31) continue;
+
+    // S^T tiles: C[key = 32*t2 + crow(r,h32)][qrow = x32], log2-scaled
+    f32x16 st[2];
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2)
+      st[t2] = mfma_rows_d128(lds_k, kf, t2, q_frag, kzero);
+    __builtin_amdgcn_s_setprio(0);
+
+    const bool diag = key0 + KVB - 1 > row_lo;
+    float mt = -INFINITY;
+    if (diag) {
+#pragma unroll
+      for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = key0 + t2 * 32 + crow(r, c.h32);
+          float s = (key <= row_me) ? st[t2][r] : -INFINITY;
+          st[t2][r] = s;
+          mt = fmaxf(mt, s);
+        }
+    } else {
+#pragma unroll
+      for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mt = fmaxf(mt, st[t2][r]);
+    }
+    mt = fmaxf(mt, __shfl_xor(mt, 32, WAVE));
+    const float m_new = fmaxf(m_run, mt);
+    const float alpha = fast_exp2(m_run - m_new);
+    float psum = 0.f;
+    PackedC P;
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+      for (int r1 = 0; r1 < 4; ++r1) {
+        float p[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          p[e] = fast_exp2(st[t2][4 * r1 + e] - m_new);
+          psum += p[e];
+        }
+        P.wA[t2][r1] = pack2(p[0], p[1]);
+        P.wB[t2][r1] = pack2(p[2], p[3]);
+      }
+    psum += __shfl_xor(psum, 32, WAVE);
+    l_run = l_run * alpha + psum;
+    m_run = m_new;
+
+    if (__any(alpha != 1.0f)) {
+      float a_row[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        a_row[r] = __shfl(alpha, crow(r, c.h32), WAVE);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o_acc[dt][r] *= a_row[r];
+    }
+
+    // O[qrow][d] += P V  (A-frag k = key)
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      mfma_cols_d128(o_acc, frag_from_packed(P, s), lds_v, trb, s);
+    __builtin_amdgcn_s_setprio(0);
+  }
+
+  __syncthreads();   // K/V tiles are consumed: their space holds the images
+  const BlockCtx e = c.fresh_lane();
+  float linv_row[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    linv_row[r] = fast_rcp(__shfl(l_run, crow(r, e.h32), WAVE));
+  const int erow_lo = e.tile * BM + e.w * 32;
+  store_ctiles128(o + e.base(so, H) + (long long)erow_lo * so.t, so.t, e,
+                  o_acc, [&](int r) { return linv_row[r]; },
+                  smem + e.w * STAGE128);
+  if (e.lane < 32)
+    lse[e.bh * T + erow_lo + e.x32] = (m_run + log2f(l_run)) * LN2;
+}
+
+template <int NW>
+__launch_bounds__(NW * WAVE, fwd_dq_waves_per_simd(NW))
+NO_PK_F32
+__global__ void attn_d128_fwd_kernel(const bf16* __restrict__ q,
+                                     const bf16* __restrict__ k,
+                                     const bf16* __restrict__ v,
+                                     bf16* __restrict__ o,
+                                     float* __restrict__ lse, int T, int H,
+                                     float scale, GStride sq, GStride so,
+                                     int balance) {
+  static_assert(NW * STAGE128 <= 2 * TILE128, "epilogue images reuse the tiles");
+  __shared__ __attribute__((aligned(16))) char smem[2 * TILE128];
+  BlockCtx c(T / (NW * 32), balance, true);
+  do {
+    d128_fwd_tile<NW>(c, smem, q, k, v, o, lse, T, H, scale, sq, so);
+  } while (c.next_pass());
+}
+
+// ---------------------------------------------------------------------------
+// Backward dQ: one workgroup per (NW*32)-row Q block; wave w owns 32 rows.
+// Computes and publishes delta for the dkv kernel, which runs after it.
+// ---------------------------------------------------------------------------
+template <int NW>
+DEV_INLINE void d128_bwd_dq_tile(const BlockCtx& c, char* smem,
+                                 const bf16* __restrict__ q,
+                                 const bf16* __restrict__ k,
+                                 const bf16* __restrict__ v,
+                                 const bf16* __restrict__ o,
+                                 const bf16* __restrict__ dout,
+                                 const float* __restrict__ lse,
+                                 float* __restrict__ delta,
+                                 bf16* __restrict__ dq, int T, int H,
+                                 float scale, const GStride& sq,
+                                 const GStride& so, const GStride& sd) {
+  constexpr int BM = NW * 32;
+  constexpr int NT = NW * WAVE;
+  char* lds_k = smem;
+  char* lds_v = smem + TILE128;
+
+  const long long boff = c.base(sq, H);
+  const long long ooff = c.base(so, H);
+  const int row_lo = c.tile * BM + c.w * 32;
+  const int row_me = row_lo + c.x32;
+
+  TilePipe<NT> pipe_k = tile128_pipe<NT>(k + boff, sq.t, c.tid);
+  TilePipe<NT> pipe_v = tile128_pipe<NT>(v + boff, sq.t, c.tid);
+  const FragOff fo(c);
+  int trb[2][2];
+  tr_bases(c.lane, trb);
+  bfrag q_frag[8], do_frag[8];
+  load_row_frags_scaled(q_frag, q + boff, row_me, c.h32, sq.t, scale * LOG2E);
+  load_row_frags(do_frag, dout + ooff, row_me, c.h32, so.t);
+  const float lse2_me = lse[c.bh * T + row_me] * LOG2E;
+  // delta = rowsum(dO*O) from the dO fragments already here plus one O load
+  float dlt_me = 0.f;
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    union { bfrag f; short8v v8; } ov, dv;
+    ov.f = load_frag(o + ooff, row_me, s * 16 + 8 * c.h32, so.t);
+    dv.f = do_frag[s];
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      dlt_me += bf_elem(ov.v8, e) * bf_elem(dv.v8, e);
+  }
+  dlt_me += __shfl_xor(dlt_me, 32, WAVE);
+  if (c.lane < 32) delta[c.bh * T + row_me] = dlt_me;
+
+  const f32x16 kzero = {};
+  f32x16 dq_acc[4] = {};
+
+  const int n_kv = (c.tile + 1) * BM / KVB;
+  pipe_k.prime();
+  pipe_v.prime();
+  for (int j = 0; j < n_kv; ++j) {
+    next_tiles128(pipe_k, lds_k, pipe_v, lds_v, j + 1 < n_kv);
+    __syncthreads();
+
+    const int key0 = j * KVB;
+    if (key0 > row_lo + 31) continue;
+
+    const bool diag = key0 + KVB - 1 > row_lo;
+    PackedC dS;
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2) {
+      // S^T, dP^T tiles: C[key = 32*t2 + crow(r,h32)][qrow = x32]
+      __builtin_amdgcn_s_setprio(1);
+      const f32x16 s_acc = mfma_rows_d128(lds_k, fo, t2, q_frag, kzero);
+      const f32x16 dp_acc = mfma_rows_d128(lds_v, fo, t2, do_frag, kzero);
+      __builtin_amdgcn_s_setprio(0);
+      float dsv[16];
+      // the mask as a compile-time split on a wave-uniform condition
+      auto consume = [&](auto MASK) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float pp = fast_exp2(s_acc[r] - lse2_me);
+          if (MASK.value) {
+            const int key = key0 + t2 * 32 + crow(r, c.h32);
+            pp = (key <= row_me) ? pp : 0.f;
+          }
+          dsv[r] = pp * (dp_acc[r] - dlt_me);   // scale in the epilogue
+        }
+      };
+      if (diag)
+        consume(std::true_type{});
+      else
+        consume(std::false_type{});
+#pragma unroll
+      for (int r1 = 0; r1 < 4; ++r1) {
+        dS.wA[t2][r1] = pack2(dsv[4 * r1], dsv[4 * r1 + 1]);
+        dS.wB[t2][r1] = pack2(dsv[4 * r1 + 2], dsv[4 * r1 + 3]);
+      }
+      // dQ[qrow][d] += dS K over this half's keys (A-frag k = key): the two
+      // k-slices of half t2 need no value of the other half
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int s = 2 * t2; s < 2 * t2 + 2; ++s)
+        mfma_cols_d128(dq_acc, frag_from_packed(dS, s), lds_k, trb, s);
+      __builtin_amdgcn_s_setprio(0);
+    }
+  }
+
+  __syncthreads();   // K/V tiles are consumed: their space holds the images
+  const BlockCtx e = c.fresh_lane();
+  const int erow_lo = e.tile * BM + e.w * 32;
+  store_ctiles128(dq + e.base(sd, H) + (long long)erow_lo * sd.t, sd.t, e,
+                  dq_acc, [&](int) { return scale; }, smem + e.w * STAGE128);
+}
+
+template <int NW>
+__launch_bounds__(NW * WAVE, fwd_dq_waves_per_simd(NW))
+NO_PK_F32
+__global__ void attn_d128_bwd_dq_kernel(const bf16* __restrict__ q,
+                                        const bf16* __restrict__ k,
+                                        const bf16* __restrict__ v,
+                                        const bf16* __restrict__ o,
+                                        const bf16* __restrict__ dout,
+                                        const float* __restrict__ lse,
+                                        float* __restrict__ delta,
+                                        bf16* __restrict__ dq, int T, int H,
+                                        float scale, GStride sq, GStride so,
+                                        GStride sd, int balance) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * TILE128];
+  BlockCtx c(T / (NW * 32), balance, true);
+  do {
+    d128_bwd_dq_tile<NW>(c, smem, q, k, v, o, dout, lse, delta, dq, T, H,
+                         scale, sq, so, sd);
+  } while (c.next_pass());
+}
+
+// ---------------------------------------------------------------------------
+// Backward dK/dV: one workgroup per (NW*32)-key block; wave w owns 32 keys
+// and streams 64-row Q/dO tiles from the diagonal to the end.
+// ---------------------------------------------------------------------------
+template <int NW>
+DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
+                                  const bf16* __restrict__ q,
+                                  const bf16* __restrict__ k,
+                                  const bf16* __restrict__ v,
+                                  const bf16* __restrict__ dout,
+                                  const float* __restrict__ lse,
+                                  const float* __restrict__ delta,
+                                  bf16* __restrict__ dk, bf16* __restrict__ dv,
+                                  int T, int H, float scale, const GStride& sq,
+                                  const GStride& so, const GStride& sd) {
+  constexpr int BK = NW * 32;
+  constexpr int NT = NW * WAVE;
+  char* lds_q = smem;
+  char* lds_do = smem + TILE128;
+  float* lds_lse = reinterpret_cast<float*>(smem + 2 * TILE128);
+  float* lds_dlt = lds_lse + KVB;
+
+  const long long boff = c.base(sq, H);
+  const int i0 = c.tile * BK / KVB;   // first Q tile that sees these keys
+  const int n_q = T / KVB;
+
+  TilePipe<NT> pipe_q =
+      tile128_pipe<NT>(q + boff + (long long)(i0 * KVB) * sq.t, sq.t, c.tid);
+  TilePipe<NT> pipe_do = tile128_pipe<NT>(
+      dout + c.base(so, H) + (long long)(i0 * KVB) * so.t, so.t, c.tid);
+  const FragOff af(c);
+  int trb[2][2];
+  tr_bases(c.lane, trb);
+  const int key_lo = c.tile * BK + c.w * 32;
+  const int key_me = key_lo + c.x32;
+  // B operands (col = key x32, d-slices): pinned in registers by the 4-wave
+  // kernel. The 2-wave kernel stages twice as much per thread (112 registers
+  // of pointers and pending chunks) and would spill, so its block's K and V,
+  // one 64 x 128 tile each, stay in LDS and wave w reads half w per use.
+  constexpr bool PINNED = NW != 2;
+  char* lds_kown = smem + 2 * TILE128 + 2 * KVB * 4;
+  char* lds_vown = lds_kown + TILE128;
+  bfrag k_frag[8], v_frag[8];
+  if constexpr (PINNED) {
+    load_row_frags_scaled(k_frag, k + boff, key_me, c.h32, sq.t,
+                          scale * LOG2E);
+    load_row_frags(v_frag, v + boff, key_me, c.h32, sq.t);
+  } else {
+    const long long koff = boff + (long long)(c.tile * BK) * sq.t;
+    __syncthreads();   // BAL_PAIRS: the previous pass has read its K and V
+    stage_tile128_scaled<NT>(lds_kown, k + koff, sq.t, c.tid, scale * LOG2E);
+    stage_tile128_scaled<NT>(lds_vown, v + koff, sq.t, c.tid, 1.0f);
+    // published by the barriers of the first loop iteration
+  }
+
+  const f32x16 kzero = {};
+  f32x16 dk_acc[4] = {};
+  f32x16 dv_acc[4] = {};
+
+  // lse (to log2 space) and delta of a Q tile travel with the tile
+  const long long row0 = c.bh * T + i0 * KVB;
+  RowPipe<> rows(lse + row0, delta + row0, lds_lse, lds_dlt, LOG2E, c.tid);
+  pipe_q.prime();
+  pipe_do.prime();
+  rows.fetch();
+  for (int i = i0; i < n_q; ++i) {
+    next_tiles128(pipe_q, lds_q, pipe_do, lds_do, i + 1 < n_q, rows);
+    __syncthreads();
+
+    const int q0 = i * KVB;
+    if (q0 + KVB - 1 < key_lo) continue;
+
+    const bool diag = q0 < key_lo + 32;
+    const int mask_lo = key_me - q0 - 4 * c.h32;   // diagonal tiles only
+    PackedC P, dS;
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2) {
+      // S, dP tiles: C[qrow = 32*t2 + crow(r,h32)][key = x32]
+      __builtin_amdgcn_s_setprio(1);
+      f32x16 s_acc, dp_acc;
+      if constexpr (PINNED) {
+        s_acc = mfma_rows_d128(lds_q, af, t2, k_frag, kzero);
+        dp_acc = mfma_rows_d128(lds_do, af, t2, v_frag, kzero);
+      } else {
+        s_acc = mfma_rows_d128(lds_q, af, t2, lds_kown, c.w, kzero);
+        dp_acc = mfma_rows_d128(lds_do, af, t2, lds_vown, c.w, kzero);
+      }
+      __builtin_amdgcn_s_setprio(0);
+      auto consume = [&](auto MASK) {
+#pragma unroll
+        for (int r1 = 0; r1 < 4; ++r1) {
+          float p[4], dsv[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = 4 * r1 + e;
+            const int lrow = t2 * 32 + crow(r, c.h32);
+            float pp = fast_exp2(s_acc[r] - lds_lse[lrow]);
+            // key_me <= q0 + lrow, the lane's part of lrow moved to mask_lo
+            if (MASK.value) pp = (t2 * 32 + crow(r, 0) >= mask_lo) ? pp : 0.f;
+            p[e] = pp;
+            dsv[e] = pp * (dp_acc[r] - lds_dlt[lrow]);   // scale in epilogue
+          }
+          P.wA[t2][r1] = pack2(p[0], p[1]);
+          P.wB[t2][r1] = pack2(p[2], p[3]);
+          dS.wA[t2][r1] = pack2(dsv[0], dsv[1]);
+          dS.wB[t2][r1] = pack2(dsv[2], dsv[3]);
+        }
+      };
+      if (diag)
+        consume(std::true_type{});
+      else
+        consume(std::false_type{});
+      // dV[key][d] += P^T dO ; dK[key][d] += dS^T Q over this half's rows
+      // (A-frag k = qrow): P and dS of one half are live at a time
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int s = 2 * t2; s < 2 * t2 + 2; ++s) {
+        mfma_cols_d128(dv_acc, frag_from_packed(P, s), lds_do, trb, s);
+        mfma_cols_d128(dk_acc, frag_from_packed(dS, s), lds_q, trb, s);
+      }
+      __builtin_amdgcn_s_setprio(0);
+    }
+  }
+
+  __syncthreads();   // Q/dO tiles are consumed: their space holds the images
+  const BlockCtx e = c.fresh_lane();
+  const int ekey_lo = e.tile * BK + e.w * 32;
+  const long long doff = e.base(sd, H) + (long long)ekey_lo * sd.t;
+  char* stage = smem + e.w * STAGE128;
+  store_ctiles128(dk + doff, sd.t, e, dk_acc, [&](int) { return scale; },
+                  stage);
+  store_ctiles128(dv + doff, sd.t, e, dv_acc, [&](int) { return 1.0f; },
+                  stage);
+}
+
+// Q and dO tiles, lse and delta of a Q tile, and in the 2-wave kernel the
+// block's own K and V.
+constexpr int dkv_lds_bytes(int nw) {
+  return 2 * TILE128 + 2 * KVB * 4 + (nw == 2 ? 2 * TILE128 : 0);
+}
+
+template <int NW>
+__launch_bounds__(NW * WAVE)
+NO_PK_F32
+__global__ void attn_d128_bwd_dkv_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k,
+    const bf16* __restrict__ v, const bf16* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    bf16* __restrict__ dk, bf16* __restrict__ dv, int T, int H, float scale,
+    GStride sq, GStride so, GStride sd, int balance) {
+  __shared__ __attribute__((aligned(16)))
+  char smem[dkv_lds_bytes(NW)];
+  BlockCtx c(T / (NW * 32), balance, false);
+  do {
+    d128_bwd_dkv_tile<NW>(c, smem, q, k, v, dout, lse, delta, dk, dv, T, H,
+                          scale, sq, so, sd);
+  } while (c.next_pass());
+}
+
+// Calls f(NW): 4-wave blocks where 128 divides T, else 2-wave blocks.
+template <typename F>
+static void d128_dispatch(int T, F f) {
+  if (T % 128 == 0)
+    f(std::integral_constant<int, 4>{});
+  else
+    f(std::integral_constant<int, 2>{});
+}
+
+}  // namespace tdsa
+
+using namespace tdsa;
+
+extern "C" {
+
+hipError_t tdsa_attn_d128_fwd(const void* q, const void* k, const void* v,
+                              void* o, float* lse, long long B, long long H,
+                              int T, float scale, const long long* sq_in,
+                              const long long* so_in, hipStream_t stream) {
+  if (T < KVB || T % KVB) return hipErrorInvalidValue;
+  const GStride sq = gstride(sq_in), so = gstride(so_in);
+  d128_dispatch(T, [&](auto nw) {
+    constexpr int NW = decltype(nw)::value;
+    constexpr auto fwd = attn_d128_fwd_kernel<NW>;
+    const TileMap m = tile_map<fwd>(T / (NW * 32), B * H, NW * WAVE);
+    hipLaunchKernelGGL(fwd, m.grid, dim3(NW * WAVE), 0, stream,
+                       (const bf16*)q, (const bf16*)k, (const bf16*)v,
+                       (bf16*)o, lse, T, (int)H, scale, sq, so, m.balance);
+  });
+  return hipGetLastError();
+}
+
+hipError_t tdsa_attn_d128_bwd(const void* q, const void* k, const void* v,
+                              const void* o, const float* lse,
+                              const void* dout, void* dq, void* dk, void* dv,
+                              float* delta, long long B, long long H, int T,
+                              float scale, const long long* sq_in,
+                              const long long* so_in, const long long* sd_in,
+                              hipStream_t stream) {
+  if (T < KVB || T % KVB) return hipErrorInvalidValue;
+  const GStride sq = gstride(sq_in), so = gstride(so_in), sd = gstride(sd_in);
+  // dq runs FIRST: it publishes delta, which dkv (same stream) consumes
+  d128_dispatch(T, [&](auto nw) {
+    constexpr int NW = decltype(nw)::value;
+    constexpr auto dq_k = attn_d128_bwd_dq_kernel<NW>;
+    constexpr auto dkv_k = attn_d128_bwd_dkv_kernel<NW>;
+    const dim3 block(NW * WAVE);
+    const int n_tiles = T / (NW * 32);
+    // the two kernels differ in residency, so each gets its own mapping
+    const TileMap mq = tile_map<dq_k>(n_tiles, B * H, NW * WAVE);
+    const TileMap mkv = tile_map<dkv_k>(n_tiles, B * H, NW * WAVE);
+    hipLaunchKernelGGL(dq_k, mq.grid, block, 0, stream, (const bf16*)q,
+                       (const bf16*)k, (const bf16*)v, (const bf16*)o,
+                       (const bf16*)dout, lse, delta, (bf16*)dq, T, (int)H,
+                       scale, sq, so, sd, mq.balance);
+    hipLaunchKernelGGL(dkv_k, mkv.grid, block, 0, stream, (const bf16*)q,
+                       (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse,
+                       delta, (bf16*)dk, (bf16*)dv, T, (int)H, scale, sq, so,
+                       sd, mkv.balance);
+  });
+  return hipGetLastError();
+}
+
+}  // extern "C"

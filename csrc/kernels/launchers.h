@@ -128,6 +128,22 @@ hipError_t tdsa_attn_bwd(const void* q, const void* k, const void* v,
                          const long long* sd, float dropout_p,
                          unsigned long long seed, hipStream_t stream);
 
+// ---- attention_d128.hip -----------------------------------------------------
+// bf16 (B, H, T, 128) tensors, causal, T % 64 == 0 and T >= 64, contiguous
+// last dim; no dropout. Strides, lse and delta as for tdsa_attn_fwd/_bwd.
+// Any other T returns hipErrorInvalidValue and launches nothing.
+hipError_t tdsa_attn_d128_fwd(const void* q, const void* k, const void* v,
+                              void* o, float* lse, long long B, long long H,
+                              int T, float scale, const long long* sq,
+                              const long long* so, hipStream_t stream);
+hipError_t tdsa_attn_d128_bwd(const void* q, const void* k, const void* v,
+                              const void* o, const float* lse,
+                              const void* dout, void* dq, void* dk, void* dv,
+                              float* delta, long long B, long long H, int T,
+                              float scale, const long long* sq,
+                              const long long* so, const long long* sd,
+                              hipStream_t stream);
+
 // ---- gemm_tn.hip ------------------------------------------------------------
 // Split count for dw = dy[M, N]^T x[M, K]; <= 0 means the shape is not taken
 // (needs M >= 1, N % 64 == 0, K % 64 == 0; a shape with M % 64, N % 128 or

@@ -1,8 +1,9 @@
 """Isolated attention kernel benchmark (fwd / bwd), with TF/s accounting.
 
 Usage (GPU box): python scripts/bench_attn.py [--T 1024] [--B 8] [--H 16]
-Any T: a length that is no multiple of 64 runs the ragged entry points (the
-tail kernels). Causal flops: ~0.5 * 2 gemms * 2*B*H*T^2*D each for fwd; bwd
+                                               [--D 64|128]
+Any T at --D 64: a length that is no multiple of 64 runs the ragged entry
+points (the tail kernels). --D 128 runs attention_d128_fwd/_bwd (T % 64 == 0). Causal flops: ~0.5 * 2 gemms * 2*B*H*T^2*D each for fwd; bwd
 ~2.5x fwd.
 
     --tree DIR     import the package from another checkout (A/B runs of two
@@ -10,7 +11,11 @@ tail kernels). Causal flops: ~0.5 * 2 gemms * 2*B*H*T^2*D each for fwd; bwd
     --composite    also time ops.attention._composite_fwd/_bwd, the path that
                    ragged T took before the tail kernels (fp32 (B,H,T,T)
                    scores: pick a --B that fits)
-    --sdpa         also time torch's scaled_dot_product_attention forward
+    --sdpa         also time torch's scaled_dot_product_attention, forward
+                   and backward (autograd)
+    --rounds N     repeat the whole set N times, the alternatives taking turns
+                   within a round; with N > 1 a closing line per measurement
+                   gives its range over the rounds
 """
 
 import argparse
@@ -38,7 +43,9 @@ def main():
     p.add_argument("--B", type=int, default=8)
     p.add_argument("--H", type=int, default=16)
     p.add_argument("--T", type=int, default=1024)
+    p.add_argument("--D", type=int, default=64, choices=(64, 128))
     p.add_argument("--iters", type=int, default=20)
+    p.add_argument("--rounds", type=int, default=1)
     p.add_argument("--tree", default=os.path.join(os.path.dirname(__file__), ".."))
     p.add_argument("--composite", action="store_true")
     p.add_argument("--sdpa", action="store_true")
@@ -47,9 +54,11 @@ def main():
     import torch
     _C = importlib.import_module("tiny_deepspeed_amd._C")
 
-    B, H, T, D = args.B, args.H, args.T, 64
+    B, H, T, D = args.B, args.H, args.T, args.D
     fwd, bwd = _C.attention_fwd, _C.attention_bwd
-    if T % 64:
+    if D == 128:
+        fwd, bwd = _C.attention_d128_fwd, _C.attention_d128_bwd
+    elif T % 64:
         fwd, bwd = _C.attention_ragged_fwd, _C.attention_ragged_bwd
     scale = 1.0 / math.sqrt(D)
     torch.manual_seed(0)
@@ -58,38 +67,59 @@ def main():
     v = torch.randn_like(q)
     o, lse = fwd(q, k, v, scale)
     do = torch.randn_like(o)
-
-    t_fwd = timeit(lambda: fwd(q, k, v, scale), args.iters)
-    t_bwd = timeit(lambda: bwd(q, k, v, o, lse, do, scale), args.iters)
     # causal effective flops
     f_fwd = 0.5 * 2 * (2 * B * H * T * T * D)
     f_bwd = 0.5 * 5 * (2 * B * H * T * T * D)  # dkv recompute S,dP + dV,dK; dq S,dP,dQ
-    tag = f"B{B} H{H} T{T}"
-    print(f"{tag} fwd: {t_fwd*1e6:8.1f} us  {f_fwd/t_fwd/1e12:7.1f} TF/s (causal-effective)")
-    print(f"{tag} bwd: {t_bwd*1e6:8.1f} us  {f_bwd/t_bwd/1e12:7.1f} TF/s (causal-effective)")
+    tag = f"B{B} H{H} T{T} D{D}"
+    seen = {}   # measurement -> times over the rounds
 
-    if args.composite:
-        att = importlib.import_module("tiny_deepspeed_amd.ops.attention")
-        torch.cuda.reset_peak_memory_stats()
-        base = torch.cuda.memory_allocated()
-        iters = max(3, args.iters // 20)
-        t_cf = timeit(lambda: att._composite_fwd(q, k, v, scale), iters, 2)
-        t_cb = timeit(lambda: att._composite_bwd(q, k, v, o, lse, do, scale),
-                      iters, 2)
-        peak = (torch.cuda.max_memory_allocated() - base) / 2**20
-        print(f"{tag} composite fwd: {t_cf*1e6:8.1f} us  bwd: {t_cb*1e6:8.1f} us  "
-              f"peak extra memory {peak:.0f} MiB")
+    def note(name, t):
+        seen.setdefault(name, []).append(t)
 
-    if args.sdpa:
-        # rocm flash attention via torch, if available
-        def sdpa():
-            return torch.nn.functional.scaled_dot_product_attention(
-                q, k, v, is_causal=True, scale=scale)
-        try:
-            t_sdpa = timeit(sdpa, args.iters)
-            print(f"{tag} torch sdpa fwd: {t_sdpa*1e6:8.1f} us  {f_fwd/t_sdpa/1e12:7.1f} TF/s")
-        except Exception as e:
-            print("sdpa failed:", e)
+    for _ in range(args.rounds):
+        t_fwd = timeit(lambda: fwd(q, k, v, scale), args.iters)
+        t_bwd = timeit(lambda: bwd(q, k, v, o, lse, do, scale), args.iters)
+        note("fwd", t_fwd)
+        note("bwd", t_bwd)
+        print(f"{tag} fwd: {t_fwd*1e6:8.1f} us  {f_fwd/t_fwd/1e12:7.1f} TF/s (causal-effective)")
+        print(f"{tag} bwd: {t_bwd*1e6:8.1f} us  {f_bwd/t_bwd/1e12:7.1f} TF/s (causal-effective)")
+
+        if args.composite:
+            att = importlib.import_module("tiny_deepspeed_amd.ops.attention")
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            iters = max(3, args.iters // 20)
+            t_cf = timeit(lambda: att._composite_fwd(q, k, v, scale), iters, 2)
+            t_cb = timeit(lambda: att._composite_bwd(q, k, v, o, lse, do, scale),
+                          iters, 2)
+            note("composite fwd", t_cf)
+            note("composite bwd", t_cb)
+            peak = (torch.cuda.max_memory_allocated() - base) / 2**20
+            print(f"{tag} composite fwd: {t_cf*1e6:8.1f} us  bwd: {t_cb*1e6:8.1f} us  "
+                  f"peak extra memory {peak:.0f} MiB")
+
+        if args.sdpa:
+            # rocm flash attention via torch, if available
+            def sdpa(*qkv):
+                return torch.nn.functional.scaled_dot_product_attention(
+                    *qkv, is_causal=True, scale=scale)
+            try:
+                t_sdpa = timeit(lambda: sdpa(q, k, v), args.iters)
+                leaves = [t.clone().requires_grad_(True) for t in (q, k, v)]
+                out = sdpa(*leaves)
+                t_sb = timeit(lambda: torch.autograd.grad(
+                    out, leaves, do, retain_graph=True), args.iters)
+                note("torch sdpa fwd", t_sdpa)
+                note("torch sdpa bwd", t_sb)
+                print(f"{tag} torch sdpa fwd: {t_sdpa*1e6:8.1f} us  {f_fwd/t_sdpa/1e12:7.1f} TF/s"
+                      f"  bwd: {t_sb*1e6:8.1f} us  {f_bwd/t_sb/1e12:7.1f} TF/s")
+            except Exception as e:
+                print("sdpa failed:", e)
+
+    if args.rounds > 1:
+        for name, ts in seen.items():
+            print(f"{tag} {name}: range {min(ts)*1e6:.1f}-{max(ts)*1e6:.1f} us "
+                  f"over {len(ts)} rounds")
 
 
 if __name__ == "__main__":

@@ -23,6 +23,7 @@ SOURCES = [
     "csrc/kernels/optim.hip",
     "csrc/kernels/gradnorm.hip",
     "csrc/kernels/attention.hip",
+    "csrc/kernels/attention_d128.hip",
     "csrc/kernels/gemm_tn.hip",
     "csrc/kernels/transpose.hip",
     "csrc/kernels/debug.hip",

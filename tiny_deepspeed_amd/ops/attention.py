@@ -12,12 +12,16 @@ RNG keyed by (seed, batch*head, qrow, key) masks/rescales P inside the
 forward and the backward kernels regenerate the identical mask from the
 saved seed — nothing is stored (r1 verdict missing item 5).
 
-Sequence length: the kernels take any T >= 1. T % 64 == 0 runs the aligned
-kernels (attention_fwd / attention_bwd of the extension); any other T their
-tail variants (attention_ragged_fwd / attention_ragged_bwd), which handle the
-partial last tile in place, so no (B,H,T,T) score tensor is ever made on the
-GPU. CPU tensors, fp32 and head dims other than 64 use the composite autograd
-path with torch dropout.
+Sequence length: the head-dim-64 kernels take any T >= 1. T % 64 == 0 runs
+the aligned kernels (attention_fwd / attention_bwd of the extension); any
+other T their tail variants (attention_ragged_fwd / attention_ragged_bwd),
+which handle the partial last tile in place, so no (B,H,T,T) score tensor is
+ever made on the GPU.
+
+Head dim 128 (csrc/kernels/attention_d128.hip, attention_d128_fwd / _bwd):
+bf16, T % 64 == 0, no fused dropout. CPU tensors, fp32, other head dims, and
+at head dim 128 ragged T or dropout, use the composite autograd path with
+torch dropout.
 """
 
 import math
@@ -65,22 +69,47 @@ def _draw_seed():
 
 
 def _kernel_supported(q):
-    """The fused CDNA4 kernels cover the GPT-2 family shapes: bf16,
-    head_dim 64, any T >= 1 (csrc/kernels/attention.hip contract). Other
-    dtypes and head dims use the composite GPU path (rocBLAS matmuls) —
+    """The fused CDNA4 kernels take bf16 with head dim 64 and any T >= 1
+    (csrc/kernels/attention.hip), or head dim 128 and T % 64 == 0
+    (csrc/kernels/attention_d128.hip). Other dtypes and head dims, and ragged
+    T at head dim 128, use the composite GPU path (rocBLAS matmuls) —
     documented, not a silent eager fallback of a supported shape."""
-    return q.dtype == torch.bfloat16 and q.shape[-1] == 64 and q.shape[-2] >= 1
+    if q.dtype != torch.bfloat16:
+        return False
+    T, D = q.shape[-2], q.shape[-1]
+    return (D == 64 and T >= 1) or (D == 128 and T >= 64 and T % 64 == 0)
+
+
+def _fused_dropout_supported(q):
+    """Dropout inside the kernels exists at head dim 64 only; at head dim 128
+    a call with dropout takes the composite path with torch dropout."""
+    return _kernel_supported(q) and q.shape[-1] == 64
+
+
+def _without_dropout(fn):
+    """A head-dim-128 entry point under the call signature of the others
+    (callers never route dropout there: _fused_dropout_supported)."""
+    def call(*args, dropout_p=0.0, seed=0):
+        if dropout_p != 0.0:
+            raise ValueError("no fused dropout at head dim 128")
+        return fn(*args)
+    return call
 
 
 def _ext_fwd(q):
-    """The extension's forward entry point for q's length: the aligned one
-    keeps its T % 64 == 0 contract, the ragged one takes the rest."""
+    """The extension's forward entry point for q's shape: head dim 128 has
+    its own; at head dim 64 the aligned one keeps its T % 64 == 0 contract
+    and the ragged one takes the rest."""
     ext = _ext.get_ext()
+    if q.shape[-1] == 128:
+        return _without_dropout(ext.attention_d128_fwd)
     return ext.attention_ragged_fwd if q.shape[-2] % 64 else ext.attention_fwd
 
 
 def _ext_bwd(q):
     ext = _ext.get_ext()
+    if q.shape[-1] == 128:
+        return _without_dropout(ext.attention_d128_bwd)
     return ext.attention_ragged_bwd if q.shape[-2] % 64 else ext.attention_bwd
 
 
@@ -251,11 +280,11 @@ def fused_causal_attention(qkv, n_head, scale=None, dropout_p=0.0,
     p = dropout_p if training else 0.0
     if p > 0.0:
         q, k, v = _packed_views(qkv, n_head)
-        if _ext.use_native(qkv) and _kernel_supported(q):
+        if _ext.use_native(qkv) and _fused_dropout_supported(q):
             # fused in-kernel dropout
             return _FusedQKVAttentionFn.apply(qkv, n_head, scale, p,
                                               _draw_seed())
-        # CPU/unsupported dtypes: unpack to the composite autograd path
+        # CPU, unsupported dtypes, head dim 128: the composite autograd path
         y = causal_attention(q.contiguous(), k.contiguous(), v.contiguous(),
                              scale, p, training)
         return y.transpose(1, 2).reshape(y.shape[0], y.shape[2], -1)
@@ -268,10 +297,10 @@ def causal_attention(q, k, v, scale=None, dropout_p=0.0, training=False):
         scale = 1.0 / math.sqrt(k.shape[-1])
     p = dropout_p if training else 0.0
     if p > 0.0:
-        if _ext.use_native(q) and _kernel_supported(q):
+        if _ext.use_native(q) and _fused_dropout_supported(q):
             # fused in-kernel dropout
             return _CausalAttentionFn.apply(q, k, v, scale, p, _draw_seed())
-        # CPU/unsupported dtypes: composite autograd path
+        # CPU, unsupported dtypes, head dim 128: composite autograd path
         T = q.shape[-2]
         s = torch.matmul(q, k.transpose(-2, -1)) * scale
         mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
