@@ -534,7 +534,8 @@ at::Tensor linear_dx_nt(at::Tensor dy2, at::Tensor w) {
 // One pass over an attention call's bf16 tensors, q first. The kernels use
 // q's extents and, per group, one tensor's strides (`lead`: q for q/k/v, o for
 // o/dout, dq for dq/dk/dv), so any other shape or stride stops here.
-// ragged: the attention_ragged_* entry points, any T >= 1.
+// ragged: the attention_ragged_* and attention_d128_ragged_* entry points,
+// any T >= 1.
 // D: the entry point's head dim (64; 128 for attention_d128_*).
 struct AttnTensor { const char* name; const at::Tensor &t, &lead; };
 static void check_attn_call(std::initializer_list<AttnTensor> tensors,
@@ -646,48 +647,79 @@ std::vector<at::Tensor> attention_ragged_bwd(
                        scale, dq_out, dk_out, dv_out, dropout_p, seed);
 }
 
-// Head dim 128: aligned T, no dropout (csrc/kernels/attention_d128.hip).
+// Head dim 128, no dropout (csrc/kernels/attention_d128.hip). As at head dim
+// 64, attention_d128_fwd/_bwd keep T % 64 == 0 and attention_d128_ragged_*
+// take any T >= 1, running the same kernels where T % 64 == 0.
+static std::vector<at::Tensor> attn_d128_fwd_call(
+    const char* op, bool ragged, at::Tensor q, at::Tensor k, at::Tensor v,
+    double scale, c10::optional<at::Tensor> out) {
+  at::Tensor o = out.has_value() ? *out : at::empty_like(q);
+  check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"out", o, o}}, 0.0,
+                  ragged, 128);
+  const long long B = q.size(0), H = q.size(1), T = q.size(2);
+  auto lse = at::empty({B, H, T}, q.options().dtype(at::kFloat));
+  const auto launch = ragged ? tdsa_attn_d128_ragged_fwd : tdsa_attn_d128_fwd;
+  check_hip(launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                   lse.data_ptr<float>(), B, H, (int)T, (float)scale,
+                   strides3(q).data(), strides3(o).data(), cur_stream()),
+            op);
+  return {o, lse};
+}
+
 std::vector<at::Tensor> attention_d128_fwd(at::Tensor q, at::Tensor k,
                                            at::Tensor v, double scale,
                                            c10::optional<at::Tensor> out) {
-  at::Tensor o = out.has_value() ? *out : at::empty_like(q);
-  check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"out", o, o}}, 0.0,
-                  false, 128);
+  return attn_d128_fwd_call("attention_d128_fwd", false, q, k, v, scale, out);
+}
+
+std::vector<at::Tensor> attention_d128_ragged_fwd(
+    at::Tensor q, at::Tensor k, at::Tensor v, double scale,
+    c10::optional<at::Tensor> out) {
+  return attn_d128_fwd_call("attention_d128_ragged_fwd", true, q, k, v, scale,
+                            out);
+}
+
+static std::vector<at::Tensor> attn_d128_bwd_call(
+    const char* op, bool ragged, at::Tensor q, at::Tensor k, at::Tensor v,
+    at::Tensor o, at::Tensor lse, at::Tensor dout, double scale,
+    c10::optional<at::Tensor> dq_out, c10::optional<at::Tensor> dk_out,
+    c10::optional<at::Tensor> dv_out) {
+  at::Tensor dq = dq_out.has_value() ? *dq_out : at::empty_like(q);
+  at::Tensor dk = dk_out.has_value() ? *dk_out : at::empty_like(k);
+  at::Tensor dv = dv_out.has_value() ? *dv_out : at::empty_like(v);
+  check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"o", o, o},
+                   {"dout", dout, o}, {"dq", dq, dq}, {"dk", dk, dq},
+                   {"dv", dv, dq}}, 0.0, ragged, 128);
   const long long B = q.size(0), H = q.size(1), T = q.size(2);
-  auto lse = at::empty({B, H, T}, q.options().dtype(at::kFloat));
-  check_hip(tdsa_attn_d128_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                               o.data_ptr(), lse.data_ptr<float>(), B, H,
-                               (int)T, (float)scale, strides3(q).data(),
-                               strides3(o).data(), cur_stream()),
-            "attention_d128_fwd");
-  return {o, lse};
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
+                  lse.numel() == B * H * T,
+              "lse must be fp32 on GPU with B*H*T elements, got ", lse.sizes());
+  auto lsec = lse.contiguous();
+  auto delta = at::empty({B, H, T}, q.options().dtype(at::kFloat));
+  const auto launch = ragged ? tdsa_attn_d128_ragged_bwd : tdsa_attn_d128_bwd;
+  check_hip(launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                   lsec.data_ptr<float>(), dout.data_ptr(), dq.data_ptr(),
+                   dk.data_ptr(), dv.data_ptr(), delta.data_ptr<float>(), B, H,
+                   (int)T, (float)scale, strides3(q).data(),
+                   strides3(o).data(), strides3(dq).data(), cur_stream()),
+            op);
+  return {dq, dk, dv};
 }
 
 std::vector<at::Tensor> attention_d128_bwd(
     at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
     at::Tensor dout, double scale, c10::optional<at::Tensor> dq_out,
     c10::optional<at::Tensor> dk_out, c10::optional<at::Tensor> dv_out) {
-  at::Tensor dq = dq_out.has_value() ? *dq_out : at::empty_like(q);
-  at::Tensor dk = dk_out.has_value() ? *dk_out : at::empty_like(k);
-  at::Tensor dv = dv_out.has_value() ? *dv_out : at::empty_like(v);
-  check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"o", o, o},
-                   {"dout", dout, o}, {"dq", dq, dq}, {"dk", dk, dq},
-                   {"dv", dv, dq}}, 0.0, false, 128);
-  const long long B = q.size(0), H = q.size(1), T = q.size(2);
-  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
-                  lse.numel() == B * H * T,
-              "lse must be fp32 on GPU with B*H*T elements, got ", lse.sizes());
-  auto lsec = lse.contiguous();
-  auto delta = at::empty({B * H * T}, q.options().dtype(at::kFloat));
-  check_hip(tdsa_attn_d128_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                               o.data_ptr(), lsec.data_ptr<float>(),
-                               dout.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-                               dv.data_ptr(), delta.data_ptr<float>(), B, H,
-                               (int)T, (float)scale, strides3(q).data(),
-                               strides3(o).data(), strides3(dq).data(),
-                               cur_stream()),
-            "attention_d128_bwd");
-  return {dq, dk, dv};
+  return attn_d128_bwd_call("attention_d128_bwd", false, q, k, v, o, lse, dout,
+                            scale, dq_out, dk_out, dv_out);
+}
+
+std::vector<at::Tensor> attention_d128_ragged_bwd(
+    at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
+    at::Tensor dout, double scale, c10::optional<at::Tensor> dq_out,
+    c10::optional<at::Tensor> dk_out, c10::optional<at::Tensor> dv_out) {
+  return attn_d128_bwd_call("attention_d128_ragged_bwd", true, q, k, v, o, lse,
+                            dout, scale, dq_out, dk_out, dv_out);
 }
 
 // ---- debug probes ---------------------------------------------------------
@@ -783,6 +815,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"),
           py::arg("dout"), py::arg("scale"), py::arg("dq") = py::none(),
           py::arg("dk") = py::none(), py::arg("dv") = py::none());
+  mod.def("attention_d128_ragged_fwd", &attention_d128_ragged_fwd,
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+          py::arg("out") = py::none());
+  mod.def("attention_d128_ragged_bwd", &attention_d128_ragged_bwd,
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+          py::arg("lse"), py::arg("dout"), py::arg("scale"),
+          py::arg("dq") = py::none(), py::arg("dk") = py::none(),
+          py::arg("dv") = py::none());
   mod.def("attention_ragged_fwd", &attention_ragged_fwd, py::arg("q"),
           py::arg("k"), py::arg("v"), py::arg("scale"),
           py::arg("out") = py::none(), py::arg("dropout_p") = 0.0,

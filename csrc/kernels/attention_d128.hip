@@ -1,4 +1,7 @@
-// Fused causal attention for head dim 128 (bf16, T % 64 == 0, no dropout).
+// Fused causal attention for head dim 128 (bf16, any T >= 1, no dropout).
+// T % 64 == 0 runs the kernels described here; any other T their tail
+// variants ("Ragged T" above the first tail kernel), which handle the partial
+// last tile and read or write no row >= T.
 //
 // Same scheme and number formats as attention.hip (head dim 64): forward with
 // online softmax in exp2 space and a natural-log lse; backward in two kernels
@@ -65,19 +68,25 @@ constexpr int STAGE128 = 32 * 128 * 2;   // a wave's [32][128] epilogue image
 constexpr int HALF = 64;             // elements from a row's left to right half
 
 // Stages one tensor's 64 x 128 tiles: image 0 <- columns 0-63, 1 <- 64-127.
-template <int NT>
-DEV_INLINE TilePipe<NT> tile128_pipe(const bf16* g, int st, int tid) {
-  return TilePipe<NT>(g, st, g + HALF, st, tid);
+// TAIL: `left` rows of the first tile exist. The pipe's two stages are the
+// halves of the SAME 64 rows, so its one row count serves both.
+template <int NT, bool TAIL = false>
+DEV_INLINE TilePipe<NT, TAIL> tile128_pipe(const bf16* g, int st, int tid,
+                                           int left = 0) {
+  return TilePipe<NT, TAIL>(g, st, g + HALF, st, tid, left);
 }
 
 // TilePipe::next for the two tensors of a loop at once, under ONE barrier
 // (each pipe's own next() would bring its own): barrier (the previous tiles
 // are consumed), pending registers -> LDS, and with `more` the loads of the
 // following tiles. `rows` rides along as in TilePipe::next. The caller places
-// the barrier that publishes the tiles.
-template <int NT, typename Rows = typename TilePipe<NT>::NoRows>
-DEV_INLINE void next_tiles128(TilePipe<NT>& x, char* lds_x, TilePipe<NT>& y,
-                              char* lds_y, bool more, Rows&& rows = Rows{}) {
+// the barrier that publishes the tiles. TAIL: this takes TilePipe::next's
+// place, so it steps each pipe's row count before the fetch as next() does.
+template <int NT, bool TAIL,
+          typename Rows = typename TilePipe<NT, TAIL>::NoRows>
+DEV_INLINE void next_tiles128(TilePipe<NT, TAIL>& x, char* lds_x,
+                              TilePipe<NT, TAIL>& y, char* lds_y, bool more,
+                              Rows&& rows = Rows{}) {
   __syncthreads();
   x.a.put(lds_x, x.pend_a);
   x.b.put(lds_x + IMG, x.pend_b);
@@ -89,6 +98,10 @@ DEV_INLINE void next_tiles128(TilePipe<NT>& x, char* lds_x, TilePipe<NT>& y,
     x.b.advance();
     y.a.advance();
     y.b.advance();
+    if constexpr (TAIL) {
+      x.left -= KVB;
+      y.left -= KVB;
+    }
     x.fetch();
     y.fetch();
     rows.advance();
@@ -97,17 +110,22 @@ DEV_INLINE void next_tiles128(TilePipe<NT>& x, char* lds_x, TilePipe<NT>& y,
 }
 
 // Pinned B operands of one row: d-slices 0..7, optionally prescaled.
+// TAIL: a row that does not exist (`ok` false) is not read and is all zeros.
+template <bool TAIL = false>
 DEV_INLINE void load_row_frags(bfrag (&f)[8], const bf16* p, int row, int h32,
-                               int st) {
-#pragma unroll
-  for (int s = 0; s < 8; ++s) f[s] = load_frag(p, row, s * 16 + 8 * h32, st);
-}
-
-DEV_INLINE void load_row_frags_scaled(bfrag (&f)[8], const bf16* p, int row,
-                                      int h32, int st, float mul) {
+                               int st, bool ok = true) {
 #pragma unroll
   for (int s = 0; s < 8; ++s)
-    f[s] = load_frag_scaled(p, row, s * 16 + 8 * h32, st, mul);
+    f[s] = load_frag<TAIL>(p, row, s * 16 + 8 * h32, st, ok);
+}
+
+template <bool TAIL = false>
+DEV_INLINE void load_row_frags_scaled(bfrag (&f)[8], const bf16* p, int row,
+                                      int h32, int st, float mul,
+                                      bool ok = true) {
+#pragma unroll
+  for (int s = 0; s < 8; ++s)
+    f[s] = load_frag_scaled<TAIL>(p, row, s * 16 + 8 * h32, st, mul, ok);
 }
 
 // acc = A(32-row half t2 of the tile at `lds`) x B(pinned row fragments),
@@ -142,14 +160,22 @@ DEV_INLINE f32x16 mfma_rows_d128(const char* lds, const FragOff& fo, int t2,
 
 // One-shot staging of the 64 x 128 tile at g (row stride st) times mul,
 // rounded to bf16, as two swizzled images at lds: 1024 chunks over NT threads.
-template <int NT>
+// TAIL: the tile has only its first `rows` rows (>= 1); a chunk of a later
+// row is not read and is zeros in LDS.
+template <int NT, bool TAIL = false>
 DEV_INLINE void stage_tile128_scaled(char* lds, const bf16* g, int st, int tid,
-                                     float mul) {
+                                     float mul, int rows = KVB) {
 #pragma unroll
   for (int rep = 0; rep < 1024 / NT; ++rep) {
     const int chunk = tid + rep * NT;
     const int row = chunk >> 4, piece = chunk & 15;
-    const short8v v = load8(g + (long long)row * st + piece * 8);
+    const bf16* src = g + (long long)row * st + piece * 8;
+    short8v v = {};
+    if constexpr (TAIL) {
+      if (row < rows) v = load8(src);
+    } else {
+      v = load8(src);
+    }
     short8v w;
 #pragma unroll
     for (int e = 0; e < 8; ++e) w[e] = bf_pack(bf_elem(v, e) * mul);
@@ -174,9 +200,12 @@ DEV_INLINE void mfma_cols_d128(f32x16 (&acc)[4], const bfrag& a,
 // (crow(r,h32), 32*dt + x32) = acc[dt][r] * mul(r) as bf16, through the
 // wave's own [32][128] LDS image and out as whole 256-byte rows (16 lanes x
 // 16 bytes, 4 rows per store instruction, 8 instructions).
-template <typename F>
+// TAIL: only the wave's first `rows` rows (any value; <= 0: none) exist and
+// are stored.
+template <bool TAIL = false, typename F>
 DEV_INLINE void store_ctiles128(bf16* p, int st, const BlockCtx& c,
-                                const f32x16 (&acc)[4], F mul, char* stage) {
+                                const f32x16 (&acc)[4], F mul, char* stage,
+                                int rows = 32) {
   bf16* img = reinterpret_cast<bf16*>(stage);
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
@@ -188,6 +217,9 @@ DEV_INLINE void store_ctiles128(bf16* p, int st, const BlockCtx& c,
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int row = 4 * i + (c.lane >> 4);
+    if constexpr (TAIL) {
+      if (row >= rows) continue;
+    }
     store8(p + row * st + piece * 8,
            *reinterpret_cast<const short8v*>(stage + row * 256 + piece * 16));
   }
@@ -204,7 +236,8 @@ constexpr int fwd_dq_waves_per_simd(int nw) { return nw == 4 ? 2 : 1; }
 // ---------------------------------------------------------------------------
 // Forward: one workgroup per (NW*32)-row Q block; wave w owns 32 rows.
 // ---------------------------------------------------------------------------
-template <int NW>
+// TAIL: ragged T, see "Ragged T" above the tail kernels.
+template <int NW, bool TAIL>
 DEV_INLINE void d128_fwd_tile(const BlockCtx& c, char* smem,
                               const bf16* __restrict__ q,
                               const bf16* __restrict__ k,
@@ -221,13 +254,14 @@ DEV_INLINE void d128_fwd_tile(const BlockCtx& c, char* smem,
   const int row_lo = c.tile * BM + c.w * 32;
   const int row_me = row_lo + c.x32;
 
-  TilePipe<NT> pipe_k = tile128_pipe<NT>(k + boff, sq.t, c.tid);
-  TilePipe<NT> pipe_v = tile128_pipe<NT>(v + boff, sq.t, c.tid);
+  auto pipe_k = tile128_pipe<NT, TAIL>(k + boff, sq.t, c.tid, T);
+  auto pipe_v = tile128_pipe<NT, TAIL>(v + boff, sq.t, c.tid, T);
   const FragOff kf(c);
   int trb[2][2];
   tr_bases(c.lane, trb);
   bfrag q_frag[8];
-  load_row_frags_scaled(q_frag, q + boff, row_me, c.h32, sq.t, scale * LOG2E);
+  load_row_frags_scaled<TAIL>(q_frag, q + boff, row_me, c.h32, sq.t,
+                              scale * LOG2E, row_me < T);
 
   const f32x16 kzero = {};
   f32x16 o_acc[4] = {};
@@ -243,6 +277,9 @@ DEV_INLINE void d128_fwd_tile(const BlockCtx& c, char* smem,
 
     const int key0 = j * KVB;
     if (key0 > row_lo + 31) continue;
+    if constexpr (TAIL) {
+      if (row_lo >= T) continue;   // a wave of padded rows only
+    }
 
     // S^T tiles: C[key = 32*t2 + crow(r,h32)][qrow = x32], log2-scaled
     f32x16 st[2];
@@ -318,10 +355,10 @@ DEV_INLINE void d128_fwd_tile(const BlockCtx& c, char* smem,
   for (int r = 0; r < 16; ++r)
     linv_row[r] = fast_rcp(__shfl(l_run, crow(r, e.h32), WAVE));
   const int erow_lo = e.tile * BM + e.w * 32;
-  store_ctiles128(o + e.base(so, H) + (long long)erow_lo * so.t, so.t, e,
-                  o_acc, [&](int r) { return linv_row[r]; },
-                  smem + e.w * STAGE128);
-  if (e.lane < 32)
+  store_ctiles128<TAIL>(o + e.base(so, H) + (long long)erow_lo * so.t, so.t,
+                        e, o_acc, [&](int r) { return linv_row[r]; },
+                        smem + e.w * STAGE128, T - erow_lo);
+  if (e.lane < 32 && (!TAIL || erow_lo + e.x32 < T))
     lse[e.bh * T + erow_lo + e.x32] = (m_run + log2f(l_run)) * LN2;
 }
 
@@ -339,7 +376,44 @@ __global__ void attn_d128_fwd_kernel(const bf16* __restrict__ q,
   __shared__ __attribute__((aligned(16))) char smem[2 * TILE128];
   BlockCtx c(T / (NW * 32), balance, true);
   do {
-    d128_fwd_tile<NW>(c, smem, q, k, v, o, lse, T, H, scale, sq, so);
+    d128_fwd_tile<NW, false>(c, smem, q, k, v, o, lse, T, H, scale, sq, so);
+  } while (c.next_pass());
+}
+
+// Ragged T (T % 64 != 0): the tail kernels. They are the kernels of this file
+// with TAIL set in their tile functions, on ceil(T / (NW*32)) blocks along T,
+// NW chosen for T rounded up to 64 (so NW*32 divides that, every K/V or Q/dO
+// loop ends at ceil(T/64) tiles and its last tile is the one that holds row
+// T-1). Rows >= T of a (batch, head) do not exist: in the packed layout "row
+// T" is row 0 of the next batch, and past the last batch it is not memory. So
+//   - no global read touches a row >= T: streamed chunks (TilePipe<NT, true>,
+//     whose row count next_tiles128 steps), pinned fragments
+//     (load_row_frags*<true>), the 2-wave dkv's own K and V
+//     (stage_tile128_scaled<NT, true>) and lse/delta (RowPipe<true>, the dq
+//     prologue) are predicated and arrive as zeros (lse: +inf);
+//   - nothing is stored to a row >= T (store_ctiles128<true>, lse, delta);
+//   - a wave whose 32 rows (keys in dkv) are all >= T skips its compute and
+//     keeps every barrier, like a wave above the diagonal.
+// A padded key is above the diagonal of every row < T, and a padded row adds
+// P = exp2(0 - inf) = 0 and dS = 0 * (0 - 0) = 0 times Q = 0, dO = 0 to dK/dV
+// of the keys < T: exact zeros, so rows < T carry the bits of the aligned
+// kernels on the problem zero-padded to ceil64(T) (same NW by construction).
+// Separate __global__ functions, so that they can take launch bounds of
+// their own; they fit the aligned kernels' (docs/kernels.md has the table).
+template <int NW>
+__launch_bounds__(NW * WAVE, fwd_dq_waves_per_simd(NW))
+NO_PK_F32
+__global__ void attn_d128_fwd_tail_kernel(const bf16* __restrict__ q,
+                                          const bf16* __restrict__ k,
+                                          const bf16* __restrict__ v,
+                                          bf16* __restrict__ o,
+                                          float* __restrict__ lse, int T,
+                                          int H, float scale, GStride sq,
+                                          GStride so, int balance) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * TILE128];
+  BlockCtx c((T + NW * 32 - 1) / (NW * 32), balance, true);
+  do {
+    d128_fwd_tile<NW, true>(c, smem, q, k, v, o, lse, T, H, scale, sq, so);
   } while (c.next_pass());
 }
 
@@ -347,7 +421,7 @@ __global__ void attn_d128_fwd_kernel(const bf16* __restrict__ q,
 // Backward dQ: one workgroup per (NW*32)-row Q block; wave w owns 32 rows.
 // Computes and publishes delta for the dkv kernel, which runs after it.
 // ---------------------------------------------------------------------------
-template <int NW>
+template <int NW, bool TAIL>
 DEV_INLINE void d128_bwd_dq_tile(const BlockCtx& c, char* smem,
                                  const bf16* __restrict__ q,
                                  const bf16* __restrict__ k,
@@ -369,28 +443,34 @@ DEV_INLINE void d128_bwd_dq_tile(const BlockCtx& c, char* smem,
   const int row_lo = c.tile * BM + c.w * 32;
   const int row_me = row_lo + c.x32;
 
-  TilePipe<NT> pipe_k = tile128_pipe<NT>(k + boff, sq.t, c.tid);
-  TilePipe<NT> pipe_v = tile128_pipe<NT>(v + boff, sq.t, c.tid);
+  // TAIL: this lane's row exists
+  const bool row_ok = !TAIL || row_me < T;
+
+  auto pipe_k = tile128_pipe<NT, TAIL>(k + boff, sq.t, c.tid, T);
+  auto pipe_v = tile128_pipe<NT, TAIL>(v + boff, sq.t, c.tid, T);
   const FragOff fo(c);
   int trb[2][2];
   tr_bases(c.lane, trb);
   bfrag q_frag[8], do_frag[8];
-  load_row_frags_scaled(q_frag, q + boff, row_me, c.h32, sq.t, scale * LOG2E);
-  load_row_frags(do_frag, dout + ooff, row_me, c.h32, so.t);
-  const float lse2_me = lse[c.bh * T + row_me] * LOG2E;
+  load_row_frags_scaled<TAIL>(q_frag, q + boff, row_me, c.h32, sq.t,
+                              scale * LOG2E, row_ok);
+  load_row_frags<TAIL>(do_frag, dout + ooff, row_me, c.h32, so.t, row_ok);
+  // a padded row: lse = +inf, so that P = exp2(s - inf) is exactly 0
+  float lse2_me = INFINITY;
+  if (row_ok) lse2_me = lse[c.bh * T + row_me] * LOG2E;
   // delta = rowsum(dO*O) from the dO fragments already here plus one O load
   float dlt_me = 0.f;
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
     union { bfrag f; short8v v8; } ov, dv;
-    ov.f = load_frag(o + ooff, row_me, s * 16 + 8 * c.h32, so.t);
+    ov.f = load_frag<TAIL>(o + ooff, row_me, s * 16 + 8 * c.h32, so.t, row_ok);
     dv.f = do_frag[s];
 #pragma unroll
     for (int e = 0; e < 8; ++e)
       dlt_me += bf_elem(ov.v8, e) * bf_elem(dv.v8, e);
   }
   dlt_me += __shfl_xor(dlt_me, 32, WAVE);
-  if (c.lane < 32) delta[c.bh * T + row_me] = dlt_me;
+  if (c.lane < 32 && row_ok) delta[c.bh * T + row_me] = dlt_me;
 
   const f32x16 kzero = {};
   f32x16 dq_acc[4] = {};
@@ -404,6 +484,9 @@ DEV_INLINE void d128_bwd_dq_tile(const BlockCtx& c, char* smem,
 
     const int key0 = j * KVB;
     if (key0 > row_lo + 31) continue;
+    if constexpr (TAIL) {
+      if (row_lo >= T) continue;   // a wave of padded rows only
+    }
 
     const bool diag = key0 + KVB - 1 > row_lo;
     PackedC dS;
@@ -449,8 +532,9 @@ DEV_INLINE void d128_bwd_dq_tile(const BlockCtx& c, char* smem,
   __syncthreads();   // K/V tiles are consumed: their space holds the images
   const BlockCtx e = c.fresh_lane();
   const int erow_lo = e.tile * BM + e.w * 32;
-  store_ctiles128(dq + e.base(sd, H) + (long long)erow_lo * sd.t, sd.t, e,
-                  dq_acc, [&](int) { return scale; }, smem + e.w * STAGE128);
+  store_ctiles128<TAIL>(dq + e.base(sd, H) + (long long)erow_lo * sd.t, sd.t,
+                        e, dq_acc, [&](int) { return scale; },
+                        smem + e.w * STAGE128, T - erow_lo);
 }
 
 template <int NW>
@@ -469,8 +553,25 @@ __global__ void attn_d128_bwd_dq_kernel(const bf16* __restrict__ q,
   __shared__ __attribute__((aligned(16))) char smem[2 * TILE128];
   BlockCtx c(T / (NW * 32), balance, true);
   do {
-    d128_bwd_dq_tile<NW>(c, smem, q, k, v, o, dout, lse, delta, dq, T, H,
-                         scale, sq, so, sd);
+    d128_bwd_dq_tile<NW, false>(c, smem, q, k, v, o, dout, lse, delta, dq, T,
+                                H, scale, sq, so, sd);
+  } while (c.next_pass());
+}
+
+template <int NW>
+__launch_bounds__(NW * WAVE, fwd_dq_waves_per_simd(NW))
+NO_PK_F32
+__global__ void attn_d128_bwd_dq_tail_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k,
+    const bf16* __restrict__ v, const bf16* __restrict__ o,
+    const bf16* __restrict__ dout, const float* __restrict__ lse,
+    float* __restrict__ delta, bf16* __restrict__ dq, int T, int H,
+    float scale, GStride sq, GStride so, GStride sd, int balance) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * TILE128];
+  BlockCtx c((T + NW * 32 - 1) / (NW * 32), balance, true);
+  do {
+    d128_bwd_dq_tile<NW, true>(c, smem, q, k, v, o, dout, lse, delta, dq, T,
+                               H, scale, sq, so, sd);
   } while (c.next_pass());
 }
 
@@ -478,7 +579,7 @@ __global__ void attn_d128_bwd_dq_kernel(const bf16* __restrict__ q,
 // Backward dK/dV: one workgroup per (NW*32)-key block; wave w owns 32 keys
 // and streams 64-row Q/dO tiles from the diagonal to the end.
 // ---------------------------------------------------------------------------
-template <int NW>
+template <int NW, bool TAIL>
 DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
                                   const bf16* __restrict__ q,
                                   const bf16* __restrict__ k,
@@ -498,12 +599,13 @@ DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
 
   const long long boff = c.base(sq, H);
   const int i0 = c.tile * BK / KVB;   // first Q tile that sees these keys
-  const int n_q = T / KVB;
+  const int n_q = TAIL ? (T + KVB - 1) / KVB : T / KVB;   // Q tiles in all
 
-  TilePipe<NT> pipe_q =
-      tile128_pipe<NT>(q + boff + (long long)(i0 * KVB) * sq.t, sq.t, c.tid);
-  TilePipe<NT> pipe_do = tile128_pipe<NT>(
-      dout + c.base(so, H) + (long long)(i0 * KVB) * so.t, so.t, c.tid);
+  auto pipe_q = tile128_pipe<NT, TAIL>(
+      q + boff + (long long)(i0 * KVB) * sq.t, sq.t, c.tid, T - i0 * KVB);
+  auto pipe_do = tile128_pipe<NT, TAIL>(
+      dout + c.base(so, H) + (long long)(i0 * KVB) * so.t, so.t, c.tid,
+      T - i0 * KVB);
   const FragOff af(c);
   int trb[2][2];
   tr_bases(c.lane, trb);
@@ -518,14 +620,17 @@ DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
   char* lds_vown = lds_kown + TILE128;
   bfrag k_frag[8], v_frag[8];
   if constexpr (PINNED) {
-    load_row_frags_scaled(k_frag, k + boff, key_me, c.h32, sq.t,
-                          scale * LOG2E);
-    load_row_frags(v_frag, v + boff, key_me, c.h32, sq.t);
+    load_row_frags_scaled<TAIL>(k_frag, k + boff, key_me, c.h32, sq.t,
+                                scale * LOG2E, key_me < T);
+    load_row_frags<TAIL>(v_frag, v + boff, key_me, c.h32, sq.t, key_me < T);
   } else {
     const long long koff = boff + (long long)(c.tile * BK) * sq.t;
     __syncthreads();   // BAL_PAIRS: the previous pass has read its K and V
-    stage_tile128_scaled<NT>(lds_kown, k + koff, sq.t, c.tid, scale * LOG2E);
-    stage_tile128_scaled<NT>(lds_vown, v + koff, sq.t, c.tid, 1.0f);
+    // TAIL: BK = 64 here, so the block's tile has T - tile * 64 >= 1 rows
+    stage_tile128_scaled<NT, TAIL>(lds_kown, k + koff, sq.t, c.tid,
+                                   scale * LOG2E, T - c.tile * BK);
+    stage_tile128_scaled<NT, TAIL>(lds_vown, v + koff, sq.t, c.tid, 1.0f,
+                                   T - c.tile * BK);
     // published by the barriers of the first loop iteration
   }
 
@@ -535,7 +640,8 @@ DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
 
   // lse (to log2 space) and delta of a Q tile travel with the tile
   const long long row0 = c.bh * T + i0 * KVB;
-  RowPipe<> rows(lse + row0, delta + row0, lds_lse, lds_dlt, LOG2E, c.tid);
+  RowPipe<TAIL> rows(lse + row0, delta + row0, lds_lse, lds_dlt, LOG2E, c.tid,
+                     T - i0 * KVB);
   pipe_q.prime();
   pipe_do.prime();
   rows.fetch();
@@ -545,6 +651,9 @@ DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
 
     const int q0 = i * KVB;
     if (q0 + KVB - 1 < key_lo) continue;
+    if constexpr (TAIL) {
+      if (key_lo >= T) continue;   // a wave of padded keys only
+    }
 
     const bool diag = q0 < key_lo + 32;
     const int mask_lo = key_me - q0 - 4 * c.h32;   // diagonal tiles only
@@ -603,10 +712,10 @@ DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
   const int ekey_lo = e.tile * BK + e.w * 32;
   const long long doff = e.base(sd, H) + (long long)ekey_lo * sd.t;
   char* stage = smem + e.w * STAGE128;
-  store_ctiles128(dk + doff, sd.t, e, dk_acc, [&](int) { return scale; },
-                  stage);
-  store_ctiles128(dv + doff, sd.t, e, dv_acc, [&](int) { return 1.0f; },
-                  stage);
+  store_ctiles128<TAIL>(dk + doff, sd.t, e, dk_acc,
+                        [&](int) { return scale; }, stage, T - ekey_lo);
+  store_ctiles128<TAIL>(dv + doff, sd.t, e, dv_acc,
+                        [&](int) { return 1.0f; }, stage, T - ekey_lo);
 }
 
 // Q and dO tiles, lse and delta of a Q tile, and in the 2-wave kernel the
@@ -628,36 +737,66 @@ __global__ void attn_d128_bwd_dkv_kernel(
   char smem[dkv_lds_bytes(NW)];
   BlockCtx c(T / (NW * 32), balance, false);
   do {
-    d128_bwd_dkv_tile<NW>(c, smem, q, k, v, dout, lse, delta, dk, dv, T, H,
-                          scale, sq, so, sd);
+    d128_bwd_dkv_tile<NW, false>(c, smem, q, k, v, dout, lse, delta, dk, dv,
+                                 T, H, scale, sq, so, sd);
   } while (c.next_pass());
 }
 
-// Calls f(NW): 4-wave blocks where 128 divides T, else 2-wave blocks.
-template <typename F>
-static void d128_dispatch(int T, F f) {
-  if (T % 128 == 0)
-    f(std::integral_constant<int, 4>{});
-  else
-    f(std::integral_constant<int, 2>{});
+template <int NW>
+__launch_bounds__(NW * WAVE)
+NO_PK_F32
+__global__ void attn_d128_bwd_dkv_tail_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k,
+    const bf16* __restrict__ v, const bf16* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    bf16* __restrict__ dk, bf16* __restrict__ dv, int T, int H, float scale,
+    GStride sq, GStride so, GStride sd, int balance) {
+  __shared__ __attribute__((aligned(16)))
+  char smem[dkv_lds_bytes(NW)];
+  BlockCtx c((T + NW * 32 - 1) / (NW * 32), balance, false);
+  do {
+    d128_bwd_dkv_tile<NW, true>(c, smem, q, k, v, dout, lse, delta, dk, dv, T,
+                                H, scale, sq, so, sd);
+  } while (c.next_pass());
 }
 
-}  // namespace tdsa
+// Calls f(NW, TAIL) as std::integral_constants. TAIL: T % 64 != 0. 4-wave
+// blocks where 128 divides T rounded up to 64, else 2-wave blocks.
+template <typename F>
+static void d128_dispatch(int T, F f) {
+  const int T64 = (T + KVB - 1) / KVB * KVB;
+  auto with_nw = [&](auto TAIL) {
+    if (T64 % 128 == 0)
+      f(std::integral_constant<int, 4>{}, TAIL);
+    else
+      f(std::integral_constant<int, 2>{}, TAIL);
+  };
+  if (T % KVB) with_nw(std::true_type{}); else with_nw(std::false_type{});
+}
 
-using namespace tdsa;
+// The three kernels of one (NW, TAIL).
+template <int NW, bool TAIL>
+struct D128Kernels {
+  static constexpr auto fwd =
+      TAIL ? attn_d128_fwd_tail_kernel<NW> : attn_d128_fwd_kernel<NW>;
+  static constexpr auto dq =
+      TAIL ? attn_d128_bwd_dq_tail_kernel<NW> : attn_d128_bwd_dq_kernel<NW>;
+  static constexpr auto dkv =
+      TAIL ? attn_d128_bwd_dkv_tail_kernel<NW> : attn_d128_bwd_dkv_kernel<NW>;
+};
 
-extern "C" {
-
-hipError_t tdsa_attn_d128_fwd(const void* q, const void* k, const void* v,
-                              void* o, float* lse, long long B, long long H,
-                              int T, float scale, const long long* sq_in,
-                              const long long* so_in, hipStream_t stream) {
-  if (T < KVB || T % KVB) return hipErrorInvalidValue;
+// Any T >= 1; the entry points below check T against their own contract.
+static hipError_t d128_launch_fwd(const void* q, const void* k, const void* v,
+                                  void* o, float* lse, long long B,
+                                  long long H, int T, float scale,
+                                  const long long* sq_in,
+                                  const long long* so_in, hipStream_t stream) {
   const GStride sq = gstride(sq_in), so = gstride(so_in);
-  d128_dispatch(T, [&](auto nw) {
+  d128_dispatch(T, [&](auto nw, auto tl) {
     constexpr int NW = decltype(nw)::value;
-    constexpr auto fwd = attn_d128_fwd_kernel<NW>;
-    const TileMap m = tile_map<fwd>(T / (NW * 32), B * H, NW * WAVE);
+    constexpr auto fwd = D128Kernels<NW, decltype(tl)::value>::fwd;
+    const int n_tiles = (T + NW * 32 - 1) / (NW * 32);
+    const TileMap m = tile_map<fwd>(n_tiles, B * H, NW * WAVE);
     hipLaunchKernelGGL(fwd, m.grid, dim3(NW * WAVE), 0, stream,
                        (const bf16*)q, (const bf16*)k, (const bf16*)v,
                        (bf16*)o, lse, T, (int)H, scale, sq, so, m.balance);
@@ -665,22 +804,23 @@ hipError_t tdsa_attn_d128_fwd(const void* q, const void* k, const void* v,
   return hipGetLastError();
 }
 
-hipError_t tdsa_attn_d128_bwd(const void* q, const void* k, const void* v,
-                              const void* o, const float* lse,
-                              const void* dout, void* dq, void* dk, void* dv,
-                              float* delta, long long B, long long H, int T,
-                              float scale, const long long* sq_in,
-                              const long long* so_in, const long long* sd_in,
-                              hipStream_t stream) {
-  if (T < KVB || T % KVB) return hipErrorInvalidValue;
+static hipError_t d128_launch_bwd(const void* q, const void* k, const void* v,
+                                  const void* o, const float* lse,
+                                  const void* dout, void* dq, void* dk,
+                                  void* dv, float* delta, long long B,
+                                  long long H, int T, float scale,
+                                  const long long* sq_in,
+                                  const long long* so_in,
+                                  const long long* sd_in, hipStream_t stream) {
   const GStride sq = gstride(sq_in), so = gstride(so_in), sd = gstride(sd_in);
   // dq runs FIRST: it publishes delta, which dkv (same stream) consumes
-  d128_dispatch(T, [&](auto nw) {
+  d128_dispatch(T, [&](auto nw, auto tl) {
     constexpr int NW = decltype(nw)::value;
-    constexpr auto dq_k = attn_d128_bwd_dq_kernel<NW>;
-    constexpr auto dkv_k = attn_d128_bwd_dkv_kernel<NW>;
+    using K = D128Kernels<NW, decltype(tl)::value>;
+    constexpr auto dq_k = K::dq;
+    constexpr auto dkv_k = K::dkv;
     const dim3 block(NW * WAVE);
-    const int n_tiles = T / (NW * 32);
+    const int n_tiles = (T + NW * 32 - 1) / (NW * 32);
     // the two kernels differ in residency, so each gets its own mapping
     const TileMap mq = tile_map<dq_k>(n_tiles, B * H, NW * WAVE);
     const TileMap mkv = tile_map<dkv_k>(n_tiles, B * H, NW * WAVE);
@@ -696,4 +836,54 @@ hipError_t tdsa_attn_d128_bwd(const void* q, const void* k, const void* v,
   return hipGetLastError();
 }
 
+}  // namespace tdsa
+
+using namespace tdsa;
+
+extern "C" {
+
+hipError_t tdsa_attn_d128_fwd(const void* q, const void* k, const void* v,
+                              void* o, float* lse, long long B, long long H,
+                              int T, float scale, const long long* sq,
+                              const long long* so, hipStream_t stream) {
+  if (T < KVB || T % KVB) return hipErrorInvalidValue;
+  return d128_launch_fwd(q, k, v, o, lse, B, H, T, scale, sq, so, stream);
+}
+
+hipError_t tdsa_attn_d128_bwd(const void* q, const void* k, const void* v,
+                              const void* o, const float* lse,
+                              const void* dout, void* dq, void* dk, void* dv,
+                              float* delta, long long B, long long H, int T,
+                              float scale, const long long* sq,
+                              const long long* so, const long long* sd,
+                              hipStream_t stream) {
+  if (T < KVB || T % KVB) return hipErrorInvalidValue;
+  return d128_launch_bwd(q, k, v, o, lse, dout, dq, dk, dv, delta, B, H, T,
+                         scale, sq, so, sd, stream);
+}
+
+hipError_t tdsa_attn_d128_ragged_fwd(const void* q, const void* k,
+                                     const void* v, void* o, float* lse,
+                                     long long B, long long H, int T,
+                                     float scale, const long long* sq,
+                                     const long long* so,
+                                     hipStream_t stream) {
+  if (T < 1) return hipErrorInvalidValue;
+  return d128_launch_fwd(q, k, v, o, lse, B, H, T, scale, sq, so, stream);
+}
+
+hipError_t tdsa_attn_d128_ragged_bwd(const void* q, const void* k,
+                                     const void* v, const void* o,
+                                     const float* lse, const void* dout,
+                                     void* dq, void* dk, void* dv,
+                                     float* delta, long long B, long long H,
+                                     int T, float scale, const long long* sq,
+                                     const long long* so, const long long* sd,
+                                     hipStream_t stream) {
+  if (T < 1) return hipErrorInvalidValue;
+  return d128_launch_bwd(q, k, v, o, lse, dout, dq, dk, dv, delta, B, H, T,
+                         scale, sq, so, sd, stream);
+}
+
 }  // extern "C"
+

@@ -143,6 +143,22 @@ hipError_t tdsa_attn_d128_bwd(const void* q, const void* k, const void* v,
                               float scale, const long long* sq,
                               const long long* so, const long long* sd,
                               hipStream_t stream);
+// The same for any T >= 1: T % 64 == 0 launches the kernels of the two entry
+// points above, any other T their tail variants, which read or write no row
+// >= T of any tensor, lse and delta ([B, H, T]) included.
+hipError_t tdsa_attn_d128_ragged_fwd(const void* q, const void* k,
+                                     const void* v, void* o, float* lse,
+                                     long long B, long long H, int T,
+                                     float scale, const long long* sq,
+                                     const long long* so, hipStream_t stream);
+hipError_t tdsa_attn_d128_ragged_bwd(const void* q, const void* k,
+                                     const void* v, const void* o,
+                                     const float* lse, const void* dout,
+                                     void* dq, void* dk, void* dv,
+                                     float* delta, long long B, long long H,
+                                     int T, float scale, const long long* sq,
+                                     const long long* so, const long long* sd,
+                                     hipStream_t stream);
 
 // ---- gemm_tn.hip ------------------------------------------------------------
 // Split count for dw = dy[M, N]^T x[M, K]; <= 0 means the shape is not taken

@@ -2,15 +2,20 @@
 
 Usage (GPU box): python scripts/bench_attn.py [--T 1024] [--B 8] [--H 16]
                                                [--D 64|128]
-Any T at --D 64: a length that is no multiple of 64 runs the ragged entry
-points (the tail kernels). --D 128 runs attention_d128_fwd/_bwd (T % 64 == 0). Causal flops: ~0.5 * 2 gemms * 2*B*H*T^2*D each for fwd; bwd
-~2.5x fwd.
+Any T at either head dim: a length that is no multiple of 64 runs the ragged
+entry points (the tail kernels); --D 128 runs attention_d128_* of the
+extension. Each figure is the mean over --iters calls between two device
+events, after warm-up. Causal flops: ~0.5 * 2 gemms * 2*B*H*T^2*D each for
+fwd; bwd ~2.5x fwd.
 
     --tree DIR     import the package from another checkout (A/B runs of two
                    builds in one session, alternating)
     --composite    also time ops.attention._composite_fwd/_bwd, the path that
                    ragged T took before the tail kernels (fp32 (B,H,T,T)
                    scores: pick a --B that fits)
+    --composite-only   time nothing else (a --tree whose extension has no
+                   kernels for the shape, such as head dim 128 at ragged T
+                   before its tail kernels)
     --sdpa         also time torch's scaled_dot_product_attention, forward
                    and backward (autograd)
     --rounds N     repeat the whole set N times, the alternatives taking turns
@@ -23,19 +28,19 @@ import importlib
 import math
 import os
 import sys
-import time
 
 
 def timeit(fn, iters=20, warmup=5):
     import torch
     for _ in range(warmup):
         fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
+    start, end = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+    start.record()
     for _ in range(iters):
         fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / iters
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) * 1e-3 / iters
 
 
 def main():
@@ -48,6 +53,7 @@ def main():
     p.add_argument("--rounds", type=int, default=1)
     p.add_argument("--tree", default=os.path.join(os.path.dirname(__file__), ".."))
     p.add_argument("--composite", action="store_true")
+    p.add_argument("--composite-only", action="store_true")
     p.add_argument("--sdpa", action="store_true")
     args = p.parse_args()
     sys.path.insert(0, os.path.abspath(args.tree))
@@ -55,17 +61,22 @@ def main():
     _C = importlib.import_module("tiny_deepspeed_amd._C")
 
     B, H, T, D = args.B, args.H, args.T, args.D
-    fwd, bwd = _C.attention_fwd, _C.attention_bwd
-    if D == 128:
-        fwd, bwd = _C.attention_d128_fwd, _C.attention_d128_bwd
-    elif T % 64:
-        fwd, bwd = _C.attention_ragged_fwd, _C.attention_ragged_bwd
+    att = importlib.import_module("tiny_deepspeed_amd.ops.attention")
+    names = {(64, False): "attention", (64, True): "attention_ragged",
+             (128, False): "attention_d128",
+             (128, True): "attention_d128_ragged"}
+    name = names[D, T % 64 != 0]
     scale = 1.0 / math.sqrt(D)
     torch.manual_seed(0)
     q = torch.randn(B, H, T, D, device="cuda", dtype=torch.bfloat16)
     k = torch.randn_like(q)
     v = torch.randn_like(q)
-    o, lse = fwd(q, k, v, scale)
+    if args.composite_only:
+        args.composite = True
+        o, lse = att._composite_fwd(q, k, v, scale)
+    else:
+        fwd, bwd = getattr(_C, name + "_fwd"), getattr(_C, name + "_bwd")
+        o, lse = fwd(q, k, v, scale)
     do = torch.randn_like(o)
     # causal effective flops
     f_fwd = 0.5 * 2 * (2 * B * H * T * T * D)
@@ -77,15 +88,15 @@ def main():
         seen.setdefault(name, []).append(t)
 
     for _ in range(args.rounds):
-        t_fwd = timeit(lambda: fwd(q, k, v, scale), args.iters)
-        t_bwd = timeit(lambda: bwd(q, k, v, o, lse, do, scale), args.iters)
-        note("fwd", t_fwd)
-        note("bwd", t_bwd)
-        print(f"{tag} fwd: {t_fwd*1e6:8.1f} us  {f_fwd/t_fwd/1e12:7.1f} TF/s (causal-effective)")
-        print(f"{tag} bwd: {t_bwd*1e6:8.1f} us  {f_bwd/t_bwd/1e12:7.1f} TF/s (causal-effective)")
+        if not args.composite_only:
+            t_fwd = timeit(lambda: fwd(q, k, v, scale), args.iters)
+            t_bwd = timeit(lambda: bwd(q, k, v, o, lse, do, scale), args.iters)
+            note("fwd", t_fwd)
+            note("bwd", t_bwd)
+            print(f"{tag} fwd: {t_fwd*1e6:8.1f} us  {f_fwd/t_fwd/1e12:7.1f} TF/s (causal-effective)")
+            print(f"{tag} bwd: {t_bwd*1e6:8.1f} us  {f_bwd/t_bwd/1e12:7.1f} TF/s (causal-effective)")
 
         if args.composite:
-            att = importlib.import_module("tiny_deepspeed_amd.ops.attention")
             torch.cuda.reset_peak_memory_stats()
             base = torch.cuda.memory_allocated()
             iters = max(3, args.iters // 20)
