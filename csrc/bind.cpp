@@ -647,49 +647,55 @@ std::vector<at::Tensor> attention_ragged_bwd(
                        scale, dq_out, dk_out, dv_out, dropout_p, seed);
 }
 
-// Head dim 128, no dropout (csrc/kernels/attention_d128.hip). As at head dim
-// 64, attention_d128_fwd/_bwd keep T % 64 == 0 and attention_d128_ragged_*
-// take any T >= 1, running the same kernels where T % 64 == 0.
+// Head dim 128 (csrc/kernels/attention_d128.hip), dropout_p and seed as at
+// head dim 64: the same (B, H, T, dropout_p, seed) is the same mask. As at
+// head dim 64, attention_d128_fwd/_bwd keep T % 64 == 0 and
+// attention_d128_ragged_* take any T >= 1, running the same kernels where
+// T % 64 == 0.
 static std::vector<at::Tensor> attn_d128_fwd_call(
     const char* op, bool ragged, at::Tensor q, at::Tensor k, at::Tensor v,
-    double scale, c10::optional<at::Tensor> out) {
+    double scale, c10::optional<at::Tensor> out, double dropout_p,
+    int64_t seed) {
   at::Tensor o = out.has_value() ? *out : at::empty_like(q);
-  check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"out", o, o}}, 0.0,
-                  ragged, 128);
+  check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"out", o, o}},
+                  dropout_p, ragged, 128);
   const long long B = q.size(0), H = q.size(1), T = q.size(2);
   auto lse = at::empty({B, H, T}, q.options().dtype(at::kFloat));
   const auto launch = ragged ? tdsa_attn_d128_ragged_fwd : tdsa_attn_d128_fwd;
   check_hip(launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                    lse.data_ptr<float>(), B, H, (int)T, (float)scale,
-                   strides3(q).data(), strides3(o).data(), cur_stream()),
+                   strides3(q).data(), strides3(o).data(), (float)dropout_p,
+                   (unsigned long long)seed, cur_stream()),
             op);
   return {o, lse};
 }
 
 std::vector<at::Tensor> attention_d128_fwd(at::Tensor q, at::Tensor k,
                                            at::Tensor v, double scale,
-                                           c10::optional<at::Tensor> out) {
-  return attn_d128_fwd_call("attention_d128_fwd", false, q, k, v, scale, out);
+                                           c10::optional<at::Tensor> out,
+                                           double dropout_p, int64_t seed) {
+  return attn_d128_fwd_call("attention_d128_fwd", false, q, k, v, scale, out,
+                            dropout_p, seed);
 }
 
 std::vector<at::Tensor> attention_d128_ragged_fwd(
     at::Tensor q, at::Tensor k, at::Tensor v, double scale,
-    c10::optional<at::Tensor> out) {
+    c10::optional<at::Tensor> out, double dropout_p, int64_t seed) {
   return attn_d128_fwd_call("attention_d128_ragged_fwd", true, q, k, v, scale,
-                            out);
+                            out, dropout_p, seed);
 }
 
 static std::vector<at::Tensor> attn_d128_bwd_call(
     const char* op, bool ragged, at::Tensor q, at::Tensor k, at::Tensor v,
     at::Tensor o, at::Tensor lse, at::Tensor dout, double scale,
     c10::optional<at::Tensor> dq_out, c10::optional<at::Tensor> dk_out,
-    c10::optional<at::Tensor> dv_out) {
+    c10::optional<at::Tensor> dv_out, double dropout_p, int64_t seed) {
   at::Tensor dq = dq_out.has_value() ? *dq_out : at::empty_like(q);
   at::Tensor dk = dk_out.has_value() ? *dk_out : at::empty_like(k);
   at::Tensor dv = dv_out.has_value() ? *dv_out : at::empty_like(v);
   check_attn_call({{"q", q, q}, {"k", k, q}, {"v", v, q}, {"o", o, o},
                    {"dout", dout, o}, {"dq", dq, dq}, {"dk", dk, dq},
-                   {"dv", dv, dq}}, 0.0, ragged, 128);
+                   {"dv", dv, dq}}, dropout_p, ragged, 128);
   const long long B = q.size(0), H = q.size(1), T = q.size(2);
   TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
                   lse.numel() == B * H * T,
@@ -701,7 +707,8 @@ static std::vector<at::Tensor> attn_d128_bwd_call(
                    lsec.data_ptr<float>(), dout.data_ptr(), dq.data_ptr(),
                    dk.data_ptr(), dv.data_ptr(), delta.data_ptr<float>(), B, H,
                    (int)T, (float)scale, strides3(q).data(),
-                   strides3(o).data(), strides3(dq).data(), cur_stream()),
+                   strides3(o).data(), strides3(dq).data(), (float)dropout_p,
+                   (unsigned long long)seed, cur_stream()),
             op);
   return {dq, dk, dv};
 }
@@ -709,17 +716,20 @@ static std::vector<at::Tensor> attn_d128_bwd_call(
 std::vector<at::Tensor> attention_d128_bwd(
     at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
     at::Tensor dout, double scale, c10::optional<at::Tensor> dq_out,
-    c10::optional<at::Tensor> dk_out, c10::optional<at::Tensor> dv_out) {
+    c10::optional<at::Tensor> dk_out, c10::optional<at::Tensor> dv_out,
+    double dropout_p, int64_t seed) {
   return attn_d128_bwd_call("attention_d128_bwd", false, q, k, v, o, lse, dout,
-                            scale, dq_out, dk_out, dv_out);
+                            scale, dq_out, dk_out, dv_out, dropout_p, seed);
 }
 
 std::vector<at::Tensor> attention_d128_ragged_bwd(
     at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
     at::Tensor dout, double scale, c10::optional<at::Tensor> dq_out,
-    c10::optional<at::Tensor> dk_out, c10::optional<at::Tensor> dv_out) {
+    c10::optional<at::Tensor> dk_out, c10::optional<at::Tensor> dv_out,
+    double dropout_p, int64_t seed) {
   return attn_d128_bwd_call("attention_d128_ragged_bwd", true, q, k, v, o, lse,
-                            dout, scale, dq_out, dk_out, dv_out);
+                            dout, scale, dq_out, dk_out, dv_out, dropout_p,
+                            seed);
 }
 
 // ---- debug probes ---------------------------------------------------------
@@ -810,19 +820,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("dropout_p") = 0.0, py::arg("seed") = 0);
   mod.def("attention_d128_fwd", &attention_d128_fwd, py::arg("q"),
           py::arg("k"), py::arg("v"), py::arg("scale"),
-          py::arg("out") = py::none());
+          py::arg("out") = py::none(), py::arg("dropout_p") = 0.0,
+          py::arg("seed") = 0);
   mod.def("attention_d128_bwd", &attention_d128_bwd, py::arg("q"),
           py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"),
           py::arg("dout"), py::arg("scale"), py::arg("dq") = py::none(),
-          py::arg("dk") = py::none(), py::arg("dv") = py::none());
+          py::arg("dk") = py::none(), py::arg("dv") = py::none(),
+          py::arg("dropout_p") = 0.0, py::arg("seed") = 0);
   mod.def("attention_d128_ragged_fwd", &attention_d128_ragged_fwd,
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
-          py::arg("out") = py::none());
+          py::arg("out") = py::none(), py::arg("dropout_p") = 0.0,
+          py::arg("seed") = 0);
   mod.def("attention_d128_ragged_bwd", &attention_d128_ragged_bwd,
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
           py::arg("lse"), py::arg("dout"), py::arg("scale"),
           py::arg("dq") = py::none(), py::arg("dk") = py::none(),
-          py::arg("dv") = py::none());
+          py::arg("dv") = py::none(), py::arg("dropout_p") = 0.0,
+          py::arg("seed") = 0);
   mod.def("attention_ragged_fwd", &attention_ragged_fwd, py::arg("q"),
           py::arg("k"), py::arg("v"), py::arg("scale"),
           py::arg("out") = py::none(), py::arg("dropout_p") = 0.0,

@@ -79,38 +79,6 @@ namespace tdsa {
 
 constexpr int D = 64;     // head dim (all GPT-2 sizes)
 
-// Value barrier (emits nothing): the compiler may not look through x. Used
-// where it otherwise rewrites the dropout code into something costlier:
-// a select moved across the bf16 pack (then done per half and re-joined with
-// v_perm_b32), or a per-tile index term folded into 32 hoisted registers.
-DEV_INLINE float pin(float x) { asm("" : "+v"(x)); return x; }
-DEV_INLINE unsigned pin(unsigned x) { asm("" : "+v"(x)); return x; }
-
-// Counter-based dropout RNG: keyed by (bh, qrow, key) so the backward
-// kernels REGENERATE the forward's mask from (seed, indices) — nothing is
-// stored, matching the recompute design. 32-bit fold + murmur3 fmix32
-// finalizer: the first splitmix64 version kept 64-bit temporaries live
-// across the softmax loop and pushed the DROP template into a 312 B/lane
-// spill — the avalanche quality of fmix32 is ample for dropout.
-// keep <=> rng < keep_thr, keep_thr = (1-p) * 2^32.
-struct Dropout {
-  unsigned long long seed;
-  unsigned keep_thr;
-  float inv_keep;   // 1 / (1-p)
-
-  DEV_INLINE bool keep(unsigned long long idx) const {
-    unsigned h = (unsigned)(idx ^ (idx >> 32));
-    h += (unsigned)seed;
-    h ^= (unsigned)(seed >> 32);
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return h < keep_thr;
-  }
-};
-
 // Epilogue of one wave's 32x64 result, held as two C tiles: element
 // (crow(r,h32), 32*dt + x32) = acc[dt][r] * mul(r), stored as bf16 at row
 // stride st from p (the wave's first row).
@@ -778,16 +746,6 @@ __global__ void attn_bwd_dq_tail_kernel(
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-
-static Dropout make_dropout(float p, unsigned long long seed) {
-  const double keepd = 1.0 - (double)p;
-  // clamp: for p -> 0, keepd*2^32 == 2^32 overflows (unsigned) to 0 and
-  // would drop EVERYTHING instead of nothing
-  const double thr_d = keepd * 4294967296.0;
-  const unsigned keep_thr =
-      thr_d >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)thr_d;
-  return {seed, keep_thr, (float)(1.0 / keepd)};
-}
 
 // Calls f(NW, DROP, TAIL) as std::integral_constants. TAIL: T % 64 != 0.
 // NW is the widest block that divides T rounded up to 64, capped by the knob

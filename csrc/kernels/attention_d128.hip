@@ -1,7 +1,8 @@
-// Fused causal attention for head dim 128 (bf16, any T >= 1, no dropout).
+// Fused causal attention for head dim 128 (bf16, any T >= 1).
 // T % 64 == 0 runs the kernels described here; any other T their tail
 // variants ("Ragged T" above the first tail kernel), which handle the partial
-// last tile and read or write no row >= T.
+// last tile and read or write no row >= T. With dropout either runs as its
+// DROP instantiation ("Dropout" above the first of those kernels).
 //
 // Same scheme and number formats as attention.hip (head dim 64): forward with
 // online softmax in exp2 space and a natural-log lse; backward in two kernels
@@ -139,15 +140,21 @@ DEV_INLINE f32x16 mfma_rows_d128(const char* lds, const FragOff& fo, int t2,
   return acc;
 }
 
-// The same with the B rows read from LDS as well: 32-row half tb of the
-// (prescaled) tile at `lds_b` (the 2-wave dkv kernel, whose staging registers
-// leave no room for pinned fragments).
+// The same with the B rows read from LDS as well: 32-row band tb of the
+// TILES (prescaled) tiles at `lds_b`, one after the other (the 2-wave dkv
+// kernel, whose staging registers leave no room for pinned fragments: one
+// tile, band = half; the 4-wave DROP dkv kernel: two tiles, four bands).
+template <int TILES = 1>
 DEV_INLINE f32x16 mfma_rows_d128(const char* lds, const FragOff& fo, int t2,
                                  const char* lds_b, int tb,
                                  const f32x16& zero) {
   // tb is a run-time value (the wave index): half tb is 32 rows of 128 bytes
   // past half 0. Indexing FragOff's row[] with it made the compiler move
   // the struct to LDS (2 KB per block).
+  if constexpr (TILES > 1) {
+    lds_b += (tb >> 1) * TILE128;
+    tb &= 1;
+  }
   lds_b += tb * (32 * 128);
   f32x16 acc = MFMA32(lds_read16(lds, fo(t2, 0)), lds_read16(lds_b, fo(0, 0)),
                       zero);
@@ -226,6 +233,12 @@ DEV_INLINE void store_ctiles128(bf16* p, int st, const BlockCtx& c,
   wave_lds_fence();   // the image is free for this wave's next result
 }
 
+// The tile functions below take the Dropout as a parameter pack, `drop_arg`:
+// empty in the kernels without dropout, one Dropout in the DROP kernels. A
+// plain parameter, even one that nothing reads, changed the register
+// allocation of the forward and dkv kernels without dropout.
+DEV_INLINE const Dropout& the_dropout(const Dropout& d) { return d; }
+
 // Waves per SIMD that the forward and dq kernels are compiled for. 2 holds
 // the 4-wave kernels to 256 registers (left alone the compiler takes 316 and
 // 344 of the 512 a lone wave may have, and a CU then holds one block, not
@@ -237,14 +250,16 @@ constexpr int fwd_dq_waves_per_simd(int nw) { return nw == 4 ? 2 : 1; }
 // Forward: one workgroup per (NW*32)-row Q block; wave w owns 32 rows.
 // ---------------------------------------------------------------------------
 // TAIL: ragged T, see "Ragged T" above the tail kernels.
-template <int NW, bool TAIL>
+// DROP: fused dropout, see "Dropout" above the DROP kernels.
+template <int NW, bool TAIL, typename... Drop>
 DEV_INLINE void d128_fwd_tile(const BlockCtx& c, char* smem,
                               const bf16* __restrict__ q,
                               const bf16* __restrict__ k,
                               const bf16* __restrict__ v,
                               bf16* __restrict__ o, float* __restrict__ lse,
                               int T, int H, float scale, const GStride& sq,
-                              const GStride& so) {
+                              const GStride& so, const Drop&... drop_arg) {
+  constexpr bool DROP = sizeof...(Drop) != 0;
   constexpr int BM = NW * 32;
   constexpr int NT = NW * WAVE;
   char* lds_k = smem;
@@ -253,6 +268,9 @@ DEV_INLINE void d128_fwd_tile(const BlockCtx& c, char* smem,
   const long long boff = c.base(sq, H);
   const int row_lo = c.tile * BM + c.w * 32;
   const int row_me = row_lo + c.x32;
+  // dropout index base of this pass's row: idx = base + key
+  unsigned long long drop_base = 0;
+  if constexpr (DROP) drop_base = ((unsigned long long)c.bh * T + row_me) * T;
 
   auto pipe_k = tile128_pipe<NT, TAIL>(k + boff, sq.t, c.tid, T);
   auto pipe_v = tile128_pipe<NT, TAIL>(v + boff, sq.t, c.tid, T);
@@ -320,7 +338,12 @@ DEV_INLINE void d128_fwd_tile(const BlockCtx& c, char* smem,
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           p[e] = fast_exp2(st[t2][4 * r1 + e] - m_new);
-          psum += p[e];
+          psum += p[e];   // the row sum is the undropped one: lse as without
+          if constexpr (DROP) {
+            const Dropout& drop = the_dropout(drop_arg...);
+            const int key = key0 + t2 * 32 + crow(4 * r1 + e, c.h32);
+            p[e] = pin(drop.keep(drop_base + key) ? p[e] * drop.inv_keep : 0.f);
+          }
         }
         P.wA[t2][r1] = pack2(p[0], p[1]);
         P.wB[t2][r1] = pack2(p[2], p[3]);
@@ -421,7 +444,7 @@ __global__ void attn_d128_fwd_tail_kernel(const bf16* __restrict__ q,
 // Backward dQ: one workgroup per (NW*32)-row Q block; wave w owns 32 rows.
 // Computes and publishes delta for the dkv kernel, which runs after it.
 // ---------------------------------------------------------------------------
-template <int NW, bool TAIL>
+template <int NW, bool TAIL, typename... Drop>
 DEV_INLINE void d128_bwd_dq_tile(const BlockCtx& c, char* smem,
                                  const bf16* __restrict__ q,
                                  const bf16* __restrict__ k,
@@ -432,7 +455,9 @@ DEV_INLINE void d128_bwd_dq_tile(const BlockCtx& c, char* smem,
                                  float* __restrict__ delta,
                                  bf16* __restrict__ dq, int T, int H,
                                  float scale, const GStride& sq,
-                                 const GStride& so, const GStride& sd) {
+                                 const GStride& so, const GStride& sd,
+                                 const Drop&... drop_arg) {
+  constexpr bool DROP = sizeof...(Drop) != 0;
   constexpr int BM = NW * 32;
   constexpr int NT = NW * WAVE;
   char* lds_k = smem;
@@ -445,6 +470,9 @@ DEV_INLINE void d128_bwd_dq_tile(const BlockCtx& c, char* smem,
 
   // TAIL: this lane's row exists
   const bool row_ok = !TAIL || row_me < T;
+  // dropout index base of this pass's row: idx = base + key
+  unsigned long long drop_base = 0;
+  if constexpr (DROP) drop_base = ((unsigned long long)c.bh * T + row_me) * T;
 
   auto pipe_k = tile128_pipe<NT, TAIL>(k + boff, sq.t, c.tid, T);
   auto pipe_v = tile128_pipe<NT, TAIL>(v + boff, sq.t, c.tid, T);
@@ -507,7 +535,13 @@ DEV_INLINE void d128_bwd_dq_tile(const BlockCtx& c, char* smem,
             const int key = key0 + t2 * 32 + crow(r, c.h32);
             pp = (key <= row_me) ? pp : 0.f;
           }
-          dsv[r] = pp * (dp_acc[r] - dlt_me);   // scale in the epilogue
+          float dpv = dp_acc[r];   // DROP: masked and rescaled before dS
+          if constexpr (DROP) {
+            const Dropout& drop = the_dropout(drop_arg...);
+            const int key = key0 + t2 * 32 + crow(r, c.h32);
+            dpv = drop.keep(drop_base + key) ? dpv * drop.inv_keep : 0.f;
+          }
+          dsv[r] = pp * (dpv - dlt_me);   // scale in the epilogue
         }
       };
       if (diag)
@@ -579,7 +613,7 @@ __global__ void attn_d128_bwd_dq_tail_kernel(
 // Backward dK/dV: one workgroup per (NW*32)-key block; wave w owns 32 keys
 // and streams 64-row Q/dO tiles from the diagonal to the end.
 // ---------------------------------------------------------------------------
-template <int NW, bool TAIL>
+template <int NW, bool TAIL, typename... Drop>
 DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
                                   const bf16* __restrict__ q,
                                   const bf16* __restrict__ k,
@@ -589,7 +623,9 @@ DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
                                   const float* __restrict__ delta,
                                   bf16* __restrict__ dk, bf16* __restrict__ dv,
                                   int T, int H, float scale, const GStride& sq,
-                                  const GStride& so, const GStride& sd) {
+                                  const GStride& so, const GStride& sd,
+                                  const Drop&... drop_arg) {
+  constexpr bool DROP = sizeof...(Drop) != 0;
   constexpr int BK = NW * 32;
   constexpr int NT = NW * WAVE;
   char* lds_q = smem;
@@ -615,9 +651,16 @@ DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
   // kernel. The 2-wave kernel stages twice as much per thread (112 registers
   // of pointers and pending chunks) and would spill, so its block's K and V,
   // one 64 x 128 tile each, stay in LDS and wave w reads half w per use.
-  constexpr bool PINNED = NW != 2;
+  // DROP: the 4-wave kernel does the same with two tiles each (128 keys;
+  // wave w reads 32-key band w), which frees the 64 registers of the pinned
+  // fragments for the mask ("Dropout" above the DROP kernels).
+  constexpr bool PINNED = (NW != 2) && !DROP;
+  constexpr int OWN = BK / KVB;   // tiles of the block's own K (and V)
   char* lds_kown = smem + 2 * TILE128 + 2 * KVB * 4;
-  char* lds_vown = lds_kown + TILE128;
+  char* lds_vown = lds_kown + OWN * TILE128;
+  // dropout index: idx = bhTT + qrow * T + key_me (qrow * T fits 32 bits)
+  unsigned long long drop_bhTT = 0;
+  if constexpr (DROP) drop_bhTT = (unsigned long long)c.bh * T * T;
   bfrag k_frag[8], v_frag[8];
   if constexpr (PINNED) {
     load_row_frags_scaled<TAIL>(k_frag, k + boff, key_me, c.h32, sq.t,
@@ -631,6 +674,16 @@ DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
                                    scale * LOG2E, T - c.tile * BK);
     stage_tile128_scaled<NT, TAIL>(lds_vown, v + koff, sq.t, c.tid, 1.0f,
                                    T - c.tile * BK);
+    if constexpr (OWN > 1) {
+      // keys 64-127 of a 4-wave block; TAIL: T rounded up to 64 is a multiple
+      // of 128, so this tile too has T - tile * 128 - 64 >= 1 rows
+      const long long koff1 = koff + (long long)KVB * sq.t;
+      stage_tile128_scaled<NT, TAIL>(lds_kown + TILE128, k + koff1, sq.t,
+                                     c.tid, scale * LOG2E,
+                                     T - c.tile * BK - KVB);
+      stage_tile128_scaled<NT, TAIL>(lds_vown + TILE128, v + koff1, sq.t,
+                                     c.tid, 1.0f, T - c.tile * BK - KVB);
+    }
     // published by the barriers of the first loop iteration
   }
 
@@ -657,6 +710,9 @@ DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
 
     const bool diag = q0 < key_lo + 32;
     const int mask_lo = key_me - q0 - 4 * c.h32;   // diagonal tiles only
+    // (q0 + lrow) * T, split like the mask: lane part here, literal at use
+    unsigned drop_rowT = 0;
+    if constexpr (DROP) drop_rowT = pin((unsigned)((q0 + 4 * c.h32) * T));
     PackedC P, dS;
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {
@@ -667,8 +723,8 @@ DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
         s_acc = mfma_rows_d128(lds_q, af, t2, k_frag, kzero);
         dp_acc = mfma_rows_d128(lds_do, af, t2, v_frag, kzero);
       } else {
-        s_acc = mfma_rows_d128(lds_q, af, t2, lds_kown, c.w, kzero);
-        dp_acc = mfma_rows_d128(lds_do, af, t2, lds_vown, c.w, kzero);
+        s_acc = mfma_rows_d128<OWN>(lds_q, af, t2, lds_kown, c.w, kzero);
+        dp_acc = mfma_rows_d128<OWN>(lds_do, af, t2, lds_vown, c.w, kzero);
       }
       __builtin_amdgcn_s_setprio(0);
       auto consume = [&](auto MASK) {
@@ -682,8 +738,19 @@ DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
             float pp = fast_exp2(s_acc[r] - lds_lse[lrow]);
             // key_me <= q0 + lrow, the lane's part of lrow moved to mask_lo
             if (MASK.value) pp = (t2 * 32 + crow(r, 0) >= mask_lo) ? pp : 0.f;
-            p[e] = pp;
-            dsv[e] = pp * (dp_acc[r] - lds_dlt[lrow]);   // scale in epilogue
+            float pv = pp;             // DROP: dropped P feeds dV,
+            float dpv = dp_acc[r];     // masked and rescaled dP feeds dS
+            if constexpr (DROP) {
+              const Dropout& drop = the_dropout(drop_arg...);
+              const bool keep = drop.keep(
+                  drop_bhTT +
+                  (drop_rowT + (unsigned)((t2 * 32 + crow(r, 0)) * T)) +
+                  key_me);
+              pv = keep ? pp * drop.inv_keep : 0.f;
+              dpv = keep ? dpv * drop.inv_keep : 0.f;
+            }
+            p[e] = pv;
+            dsv[e] = pp * (dpv - lds_dlt[lrow]);   // scale in epilogue
           }
           P.wA[t2][r1] = pack2(p[0], p[1]);
           P.wB[t2][r1] = pack2(p[2], p[3]);
@@ -718,10 +785,10 @@ DEV_INLINE void d128_bwd_dkv_tile(const BlockCtx& c, char* smem,
                         [&](int) { return 1.0f; }, stage, T - ekey_lo);
 }
 
-// Q and dO tiles, lse and delta of a Q tile, and in the 2-wave kernel the
-// block's own K and V.
-constexpr int dkv_lds_bytes(int nw) {
-  return 2 * TILE128 + 2 * KVB * 4 + (nw == 2 ? 2 * TILE128 : 0);
+// Q and dO tiles, lse and delta of a Q tile, and in the 2-wave kernel and
+// under DROP the block's own K and V (nw / 2 tiles each).
+constexpr int dkv_lds_bytes(int nw, bool drop = false) {
+  return 2 * TILE128 + 2 * KVB * 4 + (nw == 2 || drop ? nw * TILE128 : 0);
 }
 
 template <int NW>
@@ -760,22 +827,113 @@ __global__ void attn_d128_bwd_dkv_tail_kernel(
   } while (c.next_pass());
 }
 
-// Calls f(NW, TAIL) as std::integral_constants. TAIL: T % 64 != 0. 4-wave
-// blocks where 128 divides T rounded up to 64, else 2-wave blocks.
-template <typename F>
-static void d128_dispatch(int T, F f) {
-  const int T64 = (T + KVB - 1) / KVB * KVB;
-  auto with_nw = [&](auto TAIL) {
-    if (T64 % 128 == 0)
-      f(std::integral_constant<int, 4>{}, TAIL);
-    else
-      f(std::integral_constant<int, 2>{}, TAIL);
-  };
-  if (T % KVB) with_nw(std::true_type{}); else with_nw(std::false_type{});
+// ---------------------------------------------------------------------------
+// Dropout: the kernels above with DROP set in their tile functions, aligned
+// and tail, as __global__ functions of their own (their own launch bounds and
+// LDS; the kernels above keep their code). The contract is the one of
+// attention.hip, and so is the mask: score (bh, row, key) is kept where
+// Dropout::keep((bh * T + row) * T + key) holds, on the real T, whatever the
+// head dim, NW, TAIL or tile mapping. Nothing is stored: dq and dkv make the
+// forward's mask again from the seed. Every index term comes from c.tile, c.bh
+// and the lane inside the tile function, so a tile pair's second pass makes
+// its own.
+//   fwd: the row sum takes the undropped exponentials, so lse is the lse
+//        without dropout; only the packed P of P V is keep ? p / (1-p) : 0.
+//   dq : dP is masked and rescaled before dS = P (dP - delta).
+//   dkv: dV takes the dropped P; dS the undropped P and the masked dP.
+// A padded row or key (TAIL) has P = 0 before the mask and stays 0; dropout
+// reads and writes no memory.
+//
+// Registers (docs/kernels.md, "Dropout", has the table). The 4-wave forward
+// and dq sit at 238 and 250 of the 256 that two waves per SIMD allow; under
+// that cap their DROP forms keep 40-60 and 32-44 bytes of scratch per lane,
+// so they are compiled for one wave per SIMD like the 2-wave kernels (360 and
+// 360-378 registers, no scratch; a CU then holds one block of them).
+// The 4-wave dkv (486 of 512 with K and V fragments pinned) gives up the
+// pinned fragments instead: its block's K (prescaled) and V, 128 keys x 128
+// columns = two tiles each, stay in LDS after the lse/delta rows and wave w
+// reads 32-key band w per use, as the 2-wave kernel does with one tile each
+// (436-444 registers). That is 64 KB more LDS (96.5 KB per block) on a kernel
+// that ran one block per CU already.
+// ---------------------------------------------------------------------------
+constexpr int drop_waves_per_simd(int) { return 1; }
+
+template <int NW, bool TAIL>
+__launch_bounds__(NW * WAVE, drop_waves_per_simd(NW))
+NO_PK_F32
+__global__ void attn_d128_fwd_drop_kernel(const bf16* __restrict__ q,
+                                          const bf16* __restrict__ k,
+                                          const bf16* __restrict__ v,
+                                          bf16* __restrict__ o,
+                                          float* __restrict__ lse, int T,
+                                          int H, float scale, GStride sq,
+                                          GStride so, Dropout drop,
+                                          int balance) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * TILE128];
+  BlockCtx c((T + NW * 32 - 1) / (NW * 32), balance, true);
+  do {
+    d128_fwd_tile<NW, TAIL>(c, smem, q, k, v, o, lse, T, H, scale, sq,
+                                  so, drop);
+  } while (c.next_pass());
 }
 
-// The three kernels of one (NW, TAIL).
 template <int NW, bool TAIL>
+__launch_bounds__(NW * WAVE, drop_waves_per_simd(NW))
+NO_PK_F32
+__global__ void attn_d128_bwd_dq_drop_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k,
+    const bf16* __restrict__ v, const bf16* __restrict__ o,
+    const bf16* __restrict__ dout, const float* __restrict__ lse,
+    float* __restrict__ delta, bf16* __restrict__ dq, int T, int H,
+    float scale, GStride sq, GStride so, GStride sd, Dropout drop,
+    int balance) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * TILE128];
+  BlockCtx c((T + NW * 32 - 1) / (NW * 32), balance, true);
+  do {
+    d128_bwd_dq_tile<NW, TAIL>(c, smem, q, k, v, o, dout, lse, delta,
+                                     dq, T, H, scale, sq, so, sd, drop);
+  } while (c.next_pass());
+}
+
+template <int NW, bool TAIL>
+__launch_bounds__(NW * WAVE)
+NO_PK_F32
+__global__ void attn_d128_bwd_dkv_drop_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k,
+    const bf16* __restrict__ v, const bf16* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    bf16* __restrict__ dk, bf16* __restrict__ dv, int T, int H, float scale,
+    GStride sq, GStride so, GStride sd, Dropout drop, int balance) {
+  __shared__ __attribute__((aligned(16)))
+  char smem[dkv_lds_bytes(NW, true)];
+  BlockCtx c((T + NW * 32 - 1) / (NW * 32), balance, false);
+  do {
+    d128_bwd_dkv_tile<NW, TAIL>(c, smem, q, k, v, dout, lse, delta, dk,
+                                      dv, T, H, scale, sq, so, sd, drop);
+  } while (c.next_pass());
+}
+
+// Calls f(NW, TAIL, DROP) as std::integral_constants. TAIL: T % 64 != 0.
+// 4-wave blocks where 128 divides T rounded up to 64, else 2-wave blocks.
+template <typename F>
+static void d128_dispatch(int T, bool drop, F f) {
+  const int T64 = (T + KVB - 1) / KVB * KVB;
+  auto with_nw = [&](auto TAIL, auto DROP) {
+    if (T64 % 128 == 0)
+      f(std::integral_constant<int, 4>{}, TAIL, DROP);
+    else
+      f(std::integral_constant<int, 2>{}, TAIL, DROP);
+  };
+  auto with_drop = [&](auto TAIL) {
+    if (drop) with_nw(TAIL, std::true_type{});
+    else with_nw(TAIL, std::false_type{});
+  };
+  if (T % KVB) with_drop(std::true_type{}); else with_drop(std::false_type{});
+}
+
+// The three kernels of one (NW, TAIL, DROP), under one signature: the
+// kernels without dropout take no Dropout argument.
+template <int NW, bool TAIL, bool DROP>
 struct D128Kernels {
   static constexpr auto fwd =
       TAIL ? attn_d128_fwd_tail_kernel<NW> : attn_d128_fwd_kernel<NW>;
@@ -784,22 +942,45 @@ struct D128Kernels {
   static constexpr auto dkv =
       TAIL ? attn_d128_bwd_dkv_tail_kernel<NW> : attn_d128_bwd_dkv_kernel<NW>;
 };
+template <int NW, bool TAIL>
+struct D128Kernels<NW, TAIL, true> {
+  static constexpr auto fwd = attn_d128_fwd_drop_kernel<NW, TAIL>;
+  static constexpr auto dq = attn_d128_bwd_dq_drop_kernel<NW, TAIL>;
+  static constexpr auto dkv = attn_d128_bwd_dkv_drop_kernel<NW, TAIL>;
+};
+
+// Launches a kernel of either kind: `drop` goes before `balance`, the last
+// argument, where the kernel takes it.
+template <bool DROP, auto Kernel, typename... A>
+static void d128_launch(dim3 grid, int threads, hipStream_t stream,
+                        const Dropout& drop, int balance, A... a) {
+  if constexpr (DROP)
+    hipLaunchKernelGGL(Kernel, grid, dim3(threads), 0, stream, a..., drop,
+                       balance);
+  else
+    hipLaunchKernelGGL(Kernel, grid, dim3(threads), 0, stream, a..., balance);
+}
 
 // Any T >= 1; the entry points below check T against their own contract.
+// dropout_p > 0 selects the DROP instantiations and the mask of `seed`.
 static hipError_t d128_launch_fwd(const void* q, const void* k, const void* v,
                                   void* o, float* lse, long long B,
                                   long long H, int T, float scale,
                                   const long long* sq_in,
-                                  const long long* so_in, hipStream_t stream) {
+                                  const long long* so_in, float dropout_p,
+                                  unsigned long long seed,
+                                  hipStream_t stream) {
   const GStride sq = gstride(sq_in), so = gstride(so_in);
-  d128_dispatch(T, [&](auto nw, auto tl) {
+  const Dropout drop = make_dropout(dropout_p, seed);
+  d128_dispatch(T, dropout_p > 0.0f, [&](auto nw, auto tl, auto dr) {
     constexpr int NW = decltype(nw)::value;
-    constexpr auto fwd = D128Kernels<NW, decltype(tl)::value>::fwd;
+    constexpr bool DROP = decltype(dr)::value;
+    constexpr auto fwd = D128Kernels<NW, decltype(tl)::value, DROP>::fwd;
     const int n_tiles = (T + NW * 32 - 1) / (NW * 32);
     const TileMap m = tile_map<fwd>(n_tiles, B * H, NW * WAVE);
-    hipLaunchKernelGGL(fwd, m.grid, dim3(NW * WAVE), 0, stream,
-                       (const bf16*)q, (const bf16*)k, (const bf16*)v,
-                       (bf16*)o, lse, T, (int)H, scale, sq, so, m.balance);
+    d128_launch<DROP, fwd>(m.grid, NW * WAVE, stream, drop, m.balance,
+                           (const bf16*)q, (const bf16*)k, (const bf16*)v,
+                           (bf16*)o, lse, T, (int)H, scale, sq, so);
   });
   return hipGetLastError();
 }
@@ -811,27 +992,31 @@ static hipError_t d128_launch_bwd(const void* q, const void* k, const void* v,
                                   long long H, int T, float scale,
                                   const long long* sq_in,
                                   const long long* so_in,
-                                  const long long* sd_in, hipStream_t stream) {
+                                  const long long* sd_in, float dropout_p,
+                                  unsigned long long seed,
+                                  hipStream_t stream) {
   const GStride sq = gstride(sq_in), so = gstride(so_in), sd = gstride(sd_in);
+  const Dropout drop = make_dropout(dropout_p, seed);
   // dq runs FIRST: it publishes delta, which dkv (same stream) consumes
-  d128_dispatch(T, [&](auto nw, auto tl) {
+  d128_dispatch(T, dropout_p > 0.0f, [&](auto nw, auto tl, auto dr) {
     constexpr int NW = decltype(nw)::value;
-    using K = D128Kernels<NW, decltype(tl)::value>;
+    constexpr bool DROP = decltype(dr)::value;
+    using K = D128Kernels<NW, decltype(tl)::value, DROP>;
     constexpr auto dq_k = K::dq;
     constexpr auto dkv_k = K::dkv;
-    const dim3 block(NW * WAVE);
     const int n_tiles = (T + NW * 32 - 1) / (NW * 32);
     // the two kernels differ in residency, so each gets its own mapping
     const TileMap mq = tile_map<dq_k>(n_tiles, B * H, NW * WAVE);
     const TileMap mkv = tile_map<dkv_k>(n_tiles, B * H, NW * WAVE);
-    hipLaunchKernelGGL(dq_k, mq.grid, block, 0, stream, (const bf16*)q,
-                       (const bf16*)k, (const bf16*)v, (const bf16*)o,
-                       (const bf16*)dout, lse, delta, (bf16*)dq, T, (int)H,
-                       scale, sq, so, sd, mq.balance);
-    hipLaunchKernelGGL(dkv_k, mkv.grid, block, 0, stream, (const bf16*)q,
-                       (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse,
-                       delta, (bf16*)dk, (bf16*)dv, T, (int)H, scale, sq, so,
-                       sd, mkv.balance);
+    d128_launch<DROP, dq_k>(mq.grid, NW * WAVE, stream, drop, mq.balance,
+                            (const bf16*)q, (const bf16*)k, (const bf16*)v,
+                            (const bf16*)o, (const bf16*)dout, lse, delta,
+                            (bf16*)dq, T, (int)H, scale, sq, so, sd);
+    d128_launch<DROP, dkv_k>(mkv.grid, NW * WAVE, stream, drop, mkv.balance,
+                             (const bf16*)q, (const bf16*)k, (const bf16*)v,
+                             (const bf16*)dout, lse, (const float*)delta,
+                             (bf16*)dk, (bf16*)dv, T, (int)H, scale, sq, so,
+                             sd);
   });
   return hipGetLastError();
 }
@@ -845,9 +1030,11 @@ extern "C" {
 hipError_t tdsa_attn_d128_fwd(const void* q, const void* k, const void* v,
                               void* o, float* lse, long long B, long long H,
                               int T, float scale, const long long* sq,
-                              const long long* so, hipStream_t stream) {
+                              const long long* so, float dropout_p,
+                              unsigned long long seed, hipStream_t stream) {
   if (T < KVB || T % KVB) return hipErrorInvalidValue;
-  return d128_launch_fwd(q, k, v, o, lse, B, H, T, scale, sq, so, stream);
+  return d128_launch_fwd(q, k, v, o, lse, B, H, T, scale, sq, so, dropout_p,
+                         seed, stream);
 }
 
 hipError_t tdsa_attn_d128_bwd(const void* q, const void* k, const void* v,
@@ -856,20 +1043,23 @@ hipError_t tdsa_attn_d128_bwd(const void* q, const void* k, const void* v,
                               float* delta, long long B, long long H, int T,
                               float scale, const long long* sq,
                               const long long* so, const long long* sd,
+                              float dropout_p, unsigned long long seed,
                               hipStream_t stream) {
   if (T < KVB || T % KVB) return hipErrorInvalidValue;
   return d128_launch_bwd(q, k, v, o, lse, dout, dq, dk, dv, delta, B, H, T,
-                         scale, sq, so, sd, stream);
+                         scale, sq, so, sd, dropout_p, seed, stream);
 }
 
 hipError_t tdsa_attn_d128_ragged_fwd(const void* q, const void* k,
                                      const void* v, void* o, float* lse,
                                      long long B, long long H, int T,
                                      float scale, const long long* sq,
-                                     const long long* so,
+                                     const long long* so, float dropout_p,
+                                     unsigned long long seed,
                                      hipStream_t stream) {
   if (T < 1) return hipErrorInvalidValue;
-  return d128_launch_fwd(q, k, v, o, lse, B, H, T, scale, sq, so, stream);
+  return d128_launch_fwd(q, k, v, o, lse, B, H, T, scale, sq, so, dropout_p,
+                         seed, stream);
 }
 
 hipError_t tdsa_attn_d128_ragged_bwd(const void* q, const void* k,
@@ -879,11 +1069,11 @@ hipError_t tdsa_attn_d128_ragged_bwd(const void* q, const void* k,
                                      float* delta, long long B, long long H,
                                      int T, float scale, const long long* sq,
                                      const long long* so, const long long* sd,
+                                     float dropout_p, unsigned long long seed,
                                      hipStream_t stream) {
   if (T < 1) return hipErrorInvalidValue;
   return d128_launch_bwd(q, k, v, o, lse, dout, dq, dk, dv, delta, B, H, T,
-                         scale, sq, so, sd, stream);
+                         scale, sq, so, sd, dropout_p, seed, stream);
 }
 
 }  // extern "C"
-

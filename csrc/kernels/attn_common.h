@@ -2,8 +2,9 @@
 // dim 64; attention_d128.hip: head dim 128): the workgroup -> tile mapping
 // (xcd_remap, BlockCtx, tile_map), the two-tile LDS pipeline with its row
 // companion (TilePipe, RowPipe), fragment offsets and loads (FragOff,
-// load_frag*) and the C-layout -> A-fragment repack (PackedC,
-// frag_from_packed). Everything here works on 64-row tiles of swizzled
+// load_frag*), the C-layout -> A-fragment repack (PackedC,
+// frag_from_packed) and the dropout RNG (Dropout, make_dropout), one copy so
+// that both head dims realise one mask. Everything here works on 64-row tiles of swizzled
 // [64][64] bf16 images (mfma.h); nothing depends on the head dim.
 #pragma once
 
@@ -25,6 +26,51 @@ DEV_INLINE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 // Raw v_rcp_f32 for the epilogue 1/l (IEEE div emits ~10-inst div_scale
 // chains; the result feeds a bf16 store).
 DEV_INLINE float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+
+// Value barrier (emits nothing): the compiler may not look through x. Used
+// where it otherwise rewrites the dropout code into something costlier:
+// a select moved across the bf16 pack (then done per half and re-joined with
+// v_perm_b32), or a per-tile index term folded into 32 hoisted registers.
+DEV_INLINE float pin(float x) { asm("" : "+v"(x)); return x; }
+DEV_INLINE unsigned pin(unsigned x) { asm("" : "+v"(x)); return x; }
+
+// Counter-based dropout RNG: keyed by (bh, qrow, key) so the backward
+// kernels REGENERATE the forward's mask from (seed, indices) — nothing is
+// stored, matching the recompute design. 32-bit fold + murmur3 fmix32
+// finalizer: the first splitmix64 version kept 64-bit temporaries live
+// across the softmax loop and pushed the DROP template into a 312 B/lane
+// spill — the avalanche quality of fmix32 is ample for dropout.
+// keep <=> rng < keep_thr, keep_thr = (1-p) * 2^32.
+// The index of score (bh, qrow, key) is (bh * T + qrow) * T + key on the real
+// T at every head dim, block geometry and tile mapping: one (B, H, T, p,
+// seed) is one mask.
+struct Dropout {
+  unsigned long long seed;
+  unsigned keep_thr;
+  float inv_keep;   // 1 / (1-p)
+
+  DEV_INLINE bool keep(unsigned long long idx) const {
+    unsigned h = (unsigned)(idx ^ (idx >> 32));
+    h += (unsigned)seed;
+    h ^= (unsigned)(seed >> 32);
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h < keep_thr;
+  }
+};
+
+static Dropout make_dropout(float p, unsigned long long seed) {
+  const double keepd = 1.0 - (double)p;
+  // clamp: for p -> 0, keepd*2^32 == 2^32 overflows (unsigned) to 0 and
+  // would drop EVERYTHING instead of nothing
+  const double thr_d = keepd * 4294967296.0;
+  const unsigned keep_thr =
+      thr_d >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)thr_d;
+  return {seed, keep_thr, (float)(1.0 / keepd)};
+}
 
 
 // XCD-aware block remap (T1): the dispatcher places linear block b on XCD

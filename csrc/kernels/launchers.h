@@ -130,18 +130,21 @@ hipError_t tdsa_attn_bwd(const void* q, const void* k, const void* v,
 
 // ---- attention_d128.hip -----------------------------------------------------
 // bf16 (B, H, T, 128) tensors, causal, T % 64 == 0 and T >= 64, contiguous
-// last dim; no dropout. Strides, lse and delta as for tdsa_attn_fwd/_bwd.
+// last dim. Strides, lse, delta, dropout_p and seed as for tdsa_attn_fwd/_bwd:
+// equal (B, H, T, dropout_p, seed) give the mask of the head-dim-64 kernels.
 // Any other T returns hipErrorInvalidValue and launches nothing.
 hipError_t tdsa_attn_d128_fwd(const void* q, const void* k, const void* v,
                               void* o, float* lse, long long B, long long H,
                               int T, float scale, const long long* sq,
-                              const long long* so, hipStream_t stream);
+                              const long long* so, float dropout_p,
+                              unsigned long long seed, hipStream_t stream);
 hipError_t tdsa_attn_d128_bwd(const void* q, const void* k, const void* v,
                               const void* o, const float* lse,
                               const void* dout, void* dq, void* dk, void* dv,
                               float* delta, long long B, long long H, int T,
                               float scale, const long long* sq,
                               const long long* so, const long long* sd,
+                              float dropout_p, unsigned long long seed,
                               hipStream_t stream);
 // The same for any T >= 1: T % 64 == 0 launches the kernels of the two entry
 // points above, any other T their tail variants, which read or write no row
@@ -150,7 +153,9 @@ hipError_t tdsa_attn_d128_ragged_fwd(const void* q, const void* k,
                                      const void* v, void* o, float* lse,
                                      long long B, long long H, int T,
                                      float scale, const long long* sq,
-                                     const long long* so, hipStream_t stream);
+                                     const long long* so, float dropout_p,
+                                     unsigned long long seed,
+                                     hipStream_t stream);
 hipError_t tdsa_attn_d128_ragged_bwd(const void* q, const void* k,
                                      const void* v, const void* o,
                                      const float* lse, const void* dout,
@@ -158,6 +163,7 @@ hipError_t tdsa_attn_d128_ragged_bwd(const void* q, const void* k,
                                      float* delta, long long B, long long H,
                                      int T, float scale, const long long* sq,
                                      const long long* so, const long long* sd,
+                                     float dropout_p, unsigned long long seed,
                                      hipStream_t stream);
 
 // ---- gemm_tn.hip ------------------------------------------------------------

@@ -16,6 +16,11 @@ fwd; bwd ~2.5x fwd.
     --composite-only   time nothing else (a --tree whose extension has no
                    kernels for the shape, such as head dim 128 at ragged T
                    before its tail kernels)
+    --dropout P    fused dropout at rate P with a fixed seed (either head dim;
+                   default 0: the kernels without dropout). With --composite
+                   the composite is then the op layer's torch-dropout path
+                   (bf16 scores, fp32 softmax, torch dropout, autograd
+                   backward), which head dim 128 took before its DROP kernels
     --sdpa         also time torch's scaled_dot_product_attention, forward
                    and backward (autograd)
     --rounds N     repeat the whole set N times, the alternatives taking turns
@@ -50,6 +55,7 @@ def main():
     p.add_argument("--T", type=int, default=1024)
     p.add_argument("--D", type=int, default=64, choices=(64, 128))
     p.add_argument("--iters", type=int, default=20)
+    p.add_argument("--dropout", type=float, default=0.0)
     p.add_argument("--rounds", type=int, default=1)
     p.add_argument("--tree", default=os.path.join(os.path.dirname(__file__), ".."))
     p.add_argument("--composite", action="store_true")
@@ -71,17 +77,28 @@ def main():
     q = torch.randn(B, H, T, D, device="cuda", dtype=torch.bfloat16)
     k = torch.randn_like(q)
     v = torch.randn_like(q)
+    drop = {"dropout_p": args.dropout, "seed": 20240607} if args.dropout else {}
+
+    def composite_dropout(q, k, v):
+        """The composite dropout branch of ops.attention.causal_attention."""
+        s = torch.matmul(q, k.transpose(-2, -1)) * scale
+        mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
+        s = s.masked_fill(~mask, float("-inf"))
+        pm = torch.softmax(s.float(), dim=-1).to(q.dtype)
+        pm = torch.nn.functional.dropout(pm, p=args.dropout, training=True)
+        return torch.matmul(pm, v)
+
     if args.composite_only:
         args.composite = True
         o, lse = att._composite_fwd(q, k, v, scale)
     else:
         fwd, bwd = getattr(_C, name + "_fwd"), getattr(_C, name + "_bwd")
-        o, lse = fwd(q, k, v, scale)
+        o, lse = fwd(q, k, v, scale, **drop)
     do = torch.randn_like(o)
     # causal effective flops
     f_fwd = 0.5 * 2 * (2 * B * H * T * T * D)
     f_bwd = 0.5 * 5 * (2 * B * H * T * T * D)  # dkv recompute S,dP + dV,dK; dq S,dP,dQ
-    tag = f"B{B} H{H} T{T} D{D}"
+    tag = f"B{B} H{H} T{T} D{D}" + (f" p{args.dropout}" if drop else "")
     seen = {}   # measurement -> times over the rounds
 
     def note(name, t):
@@ -89,8 +106,9 @@ def main():
 
     for _ in range(args.rounds):
         if not args.composite_only:
-            t_fwd = timeit(lambda: fwd(q, k, v, scale), args.iters)
-            t_bwd = timeit(lambda: bwd(q, k, v, o, lse, do, scale), args.iters)
+            t_fwd = timeit(lambda: fwd(q, k, v, scale, **drop), args.iters)
+            t_bwd = timeit(lambda: bwd(q, k, v, o, lse, do, scale, **drop),
+                           args.iters)
             note("fwd", t_fwd)
             note("bwd", t_bwd)
             print(f"{tag} fwd: {t_fwd*1e6:8.1f} us  {f_fwd/t_fwd/1e12:7.1f} TF/s (causal-effective)")
@@ -100,9 +118,18 @@ def main():
             torch.cuda.reset_peak_memory_stats()
             base = torch.cuda.memory_allocated()
             iters = max(3, args.iters // 20)
-            t_cf = timeit(lambda: att._composite_fwd(q, k, v, scale), iters, 2)
-            t_cb = timeit(lambda: att._composite_bwd(q, k, v, o, lse, do, scale),
-                          iters, 2)
+            if drop:
+                leaves = [t.clone().requires_grad_(True) for t in (q, k, v)]
+                t_cf = timeit(lambda: composite_dropout(q, k, v), iters, 2)
+                out = composite_dropout(*leaves)
+                t_cb = timeit(lambda: torch.autograd.grad(
+                    out, leaves, do, retain_graph=True), iters, 2)
+                del out
+            else:
+                t_cf = timeit(lambda: att._composite_fwd(q, k, v, scale),
+                              iters, 2)
+                t_cb = timeit(lambda: att._composite_bwd(q, k, v, o, lse, do,
+                                                         scale), iters, 2)
             note("composite fwd", t_cf)
             note("composite bwd", t_cb)
             peak = (torch.cuda.max_memory_allocated() - base) / 2**20

@@ -19,9 +19,10 @@ attention_d128_fwd / _bwd at head dim 128); any other T their tail variants
 the partial last tile in place, so no (B,H,T,T) score tensor is ever made on
 the GPU.
 
-Head dim 128 (csrc/kernels/attention_d128.hip): bf16, no fused dropout. CPU
-tensors, fp32, other head dims, and head dim 128 with dropout, use the
-composite autograd path with torch dropout.
+Head dim 128 (csrc/kernels/attention_d128.hip): bf16, with the same fused
+dropout; equal (B, H, T, p, seed) give the mask of the head-dim-64 kernels.
+CPU tensors, fp32 and other head dims use the composite autograd path, with
+torch dropout.
 """
 
 import math
@@ -81,19 +82,8 @@ def _kernel_supported(q):
 
 
 def _fused_dropout_supported(q):
-    """Dropout inside the kernels exists at head dim 64 only; at head dim 128
-    a call with dropout takes the composite path with torch dropout."""
-    return _kernel_supported(q) and q.shape[-1] == 64
-
-
-def _without_dropout(fn):
-    """A head-dim-128 entry point under the call signature of the others
-    (callers never route dropout there: _fused_dropout_supported)."""
-    def call(*args, dropout_p=0.0, seed=0):
-        if dropout_p != 0.0:
-            raise ValueError("no fused dropout at head dim 128")
-        return fn(*args)
-    return call
+    """Dropout is fused wherever the kernels run, at both head dims."""
+    return _kernel_supported(q)
 
 
 def _ext_fwd(q):
@@ -103,8 +93,7 @@ def _ext_fwd(q):
     ext = _ext.get_ext()
     ragged = q.shape[-2] % 64 != 0
     if q.shape[-1] == 128:
-        return _without_dropout(ext.attention_d128_ragged_fwd if ragged
-                                else ext.attention_d128_fwd)
+        return ext.attention_d128_ragged_fwd if ragged else ext.attention_d128_fwd
     return ext.attention_ragged_fwd if ragged else ext.attention_fwd
 
 
@@ -112,8 +101,7 @@ def _ext_bwd(q):
     ext = _ext.get_ext()
     ragged = q.shape[-2] % 64 != 0
     if q.shape[-1] == 128:
-        return _without_dropout(ext.attention_d128_ragged_bwd if ragged
-                                else ext.attention_d128_bwd)
+        return ext.attention_d128_ragged_bwd if ragged else ext.attention_d128_bwd
     return ext.attention_ragged_bwd if ragged else ext.attention_bwd
 
 
@@ -288,7 +276,7 @@ def fused_causal_attention(qkv, n_head, scale=None, dropout_p=0.0,
             # fused in-kernel dropout
             return _FusedQKVAttentionFn.apply(qkv, n_head, scale, p,
                                               _draw_seed())
-        # CPU, unsupported dtypes, head dim 128: the composite autograd path
+        # CPU, unsupported dtypes and head dims: the composite autograd path
         y = causal_attention(q.contiguous(), k.contiguous(), v.contiguous(),
                              scale, p, training)
         return y.transpose(1, 2).reshape(y.shape[0], y.shape[2], -1)
@@ -304,7 +292,7 @@ def causal_attention(q, k, v, scale=None, dropout_p=0.0, training=False):
         if _ext.use_native(q) and _fused_dropout_supported(q):
             # fused in-kernel dropout
             return _CausalAttentionFn.apply(q, k, v, scale, p, _draw_seed())
-        # CPU, unsupported dtypes, head dim 128: composite autograd path
+        # CPU, unsupported dtypes and head dims: composite autograd path
         T = q.shape[-2]
         s = torch.matmul(q, k.transpose(-2, -1)) * scale
         mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
