@@ -152,6 +152,79 @@ std::vector<at::Tensor> layernorm_bwd_dx(at::Tensor dy, at::Tensor x,
   return {dx, pdw, pdb};
 }
 
+// Residual dropout: h = x + dropout(res, p) and y = LN(h), the mask from
+// `seed` (launchers.h). Row-per-wave shapes only; any other is an error.
+void ln_drop_args(const char* op, double p, int64_t seed) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, op, ": p must be in [0, 1), got ", p);
+  TORCH_CHECK(seed >= 0, op, ": seed must be non-negative, got ", seed);
+}
+
+std::vector<at::Tensor> layernorm_dropout_fwd(at::Tensor x, at::Tensor res,
+                                              at::Tensor w, at::Tensor b,
+                                              double eps, double p,
+                                              int64_t seed) {
+  const char* op = "layernorm_dropout_fwd";
+  int M, N;
+  ln_rows(op, x, &M, &N);
+  const int flag = check_call(op, {{"x", x, {}, kAny},
+                                   {"res", res, {}, x.numel()},
+                                   {"w", w, {}, N}, {"b", b, {}, N}});
+  ln_drop_args(op, p, seed);
+  auto y = at::empty_like(x);
+  auto h = at::empty_like(x);
+  auto f32 = x.options().dtype(at::kFloat);
+  auto mean = at::empty({M}, f32);
+  auto rstd = at::empty({M}, f32);
+  check_hip(tdsa_ln_drop_fwd(x.data_ptr(), res.data_ptr(), h.data_ptr(),
+                             w.data_ptr(), b.data_ptr(), y.data_ptr(),
+                             mean.data_ptr<float>(), rstd.data_ptr<float>(), M,
+                             N, (float)eps, (float)p,
+                             (unsigned long long)seed, flag, cur_stream()),
+            op);
+  auto row_sizes = x.sizes().vec();
+  row_sizes.pop_back();
+  return {y, mean.view(row_sizes), rstd.view(row_sizes), h};
+}
+
+// -> [dx, dres, pdw, pdb]: layernorm_bwd_dx (x is the forward's h) plus the
+// gradient of the dropped branch under the forward's mask.
+std::vector<at::Tensor> layernorm_dropout_bwd_dx(
+    at::Tensor dy, at::Tensor h, at::Tensor w, at::Tensor mean,
+    at::Tensor rstd, c10::optional<at::Tensor> dh, double p, int64_t seed) {
+  const char* op = "layernorm_dropout_bwd_dx";
+  int M, N;
+  ln_rows(op, h, &M, &N);
+  const int flag = check_call(op, {{"h", h, {}, kAny},
+                                   {"dy", dy, {}, h.numel()},
+                                   {"w", w, {}, N},
+                                   {"mean", mean, at::kFloat, M, true},
+                                   {"rstd", rstd, at::kFloat, M, true},
+                                   {"dh", dh, {}, h.numel(), true}});
+  ln_drop_args(op, p, seed);
+  const int G = tdsa_ln_bwd_dx_stripes(M, N, flag);
+  auto dx = at::empty_like(h);
+  auto dres = at::empty_like(h);
+  auto f32 = h.options().dtype(at::kFloat);
+  auto pdw = at::empty({G, N}, f32);
+  auto pdb = at::empty({G, N}, f32);
+  auto meanc = mean.contiguous();
+  auto rstdc = rstd.contiguous();
+  at::Tensor dhc;
+  void* dh_p = nullptr;
+  if (dh.has_value()) {
+    dhc = dh->contiguous();
+    dh_p = dhc.data_ptr();
+  }
+  check_hip(tdsa_ln_drop_bwd_dx(dy.data_ptr(), dh_p, h.data_ptr(),
+                                w.data_ptr(), meanc.data_ptr<float>(),
+                                rstdc.data_ptr<float>(), dx.data_ptr(),
+                                dres.data_ptr(), pdw.data_ptr<float>(),
+                                pdb.data_ptr<float>(), M, N, (float)p,
+                                (unsigned long long)seed, flag, cur_stream()),
+            op);
+  return {dx, dres, pdw, pdb};
+}
+
 // dtype: output dtype of dw/db (float32 or bfloat16, rounded in-kernel from
 // the fp32 sums); fp32 when absent.
 std::vector<at::Tensor> layernorm_bwd_dwdb(
@@ -782,6 +855,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("layernorm_bwd_dx", &layernorm_bwd_dx, py::arg("dy"), py::arg("x"),
           py::arg("w"), py::arg("mean"), py::arg("rstd"),
           py::arg("dh") = py::none());
+  mod.def("layernorm_dropout_fwd", &layernorm_dropout_fwd, py::arg("x"),
+          py::arg("res"), py::arg("w"), py::arg("b"), py::arg("eps"),
+          py::arg("p"), py::arg("seed"));
+  mod.def("layernorm_dropout_bwd_dx", &layernorm_dropout_bwd_dx,
+          py::arg("dy"), py::arg("h"), py::arg("w"), py::arg("mean"),
+          py::arg("rstd"), py::arg("dh"), py::arg("p"), py::arg("seed"));
   mod.def("layernorm_bwd_dwdb", &layernorm_bwd_dwdb, py::arg("pdw"),
           py::arg("pdb"), py::arg("dtype") = py::none());
   mod.def("layernorm_rowwave_geometry", &layernorm_rowwave_geometry,

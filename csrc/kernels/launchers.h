@@ -38,6 +38,23 @@ hipError_t tdsa_ln_bwd_dx(const void* dy, const void* dh, const void* x,
                           const void* w, const float* mean, const float* rstd,
                           void* dx, float* pdw, float* pdb, int M, int N,
                           int is_bf16, hipStream_t stream);
+// Residual dropout: tdsa_ln_fwd with h = x + (keep ? res / (1 - p) : 0), and
+// tdsa_ln_bwd_dx with the second output dres = keep ? dx / (1 - p) : 0 (from
+// the fp32 dx). Element (row, col) is kept iff the attention kernels' hash of
+// `seed` keeps index row * N + col; no mask is read or written. Row-per-wave
+// shapes only (bf16, N % 8 == 0, N <= 2048, TDSA_LN_ROWWAVE on): any other
+// shape returns hipErrorInvalidValue and launches nothing. 0 <= p < 1.
+hipError_t tdsa_ln_drop_fwd(const void* x, const void* res, void* h,
+                            const void* w, const void* b, void* y, float* mean,
+                            float* rstd, int M, int N, float eps, float p,
+                            unsigned long long seed, int is_bf16,
+                            hipStream_t stream);
+hipError_t tdsa_ln_drop_bwd_dx(const void* dy, const void* dh, const void* x,
+                               const void* w, const float* mean,
+                               const float* rstd, void* dx, void* dres,
+                               float* pdw, float* pdb, int M, int N, float p,
+                               unsigned long long seed, int is_bf16,
+                               hipStream_t stream);
 // dw, db [N] = column sums of pdw, pdb [G, N]; out_bf16 picks their dtype.
 hipError_t tdsa_ln_bwd_dwdb(const float* pdw, const float* pdb, void* dw,
                             void* db, int G, int N, int out_bf16,

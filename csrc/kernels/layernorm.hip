@@ -8,6 +8,7 @@
 // (SURVEY.md 2.10A). bf16 rows up to N=2048 run on the row-per-wave kernels
 // (one wave per row, dw/db partials in registers); fp32 and wider rows on
 // the workgroup-per-row and wide kernels.
+#include "attn_common.h"   // Dropout, make_dropout: the one mask hash
 #include "common.h"
 #include "launchers.h"
 
@@ -493,6 +494,275 @@ __global__ __launch_bounds__(LN_RW_BLOCK) void ln_bwd_rowwave_kernel(
   }
 }
 
+// ---- residual dropout (row-per-wave) -----------------------------------------
+// h = x + dropout(res) and its backward as kernels of their own: the kernels
+// above with the mask worked in. They are separate __global__ functions and
+// not a template flag of those, because moving the shared text into an
+// inlined body changed the register allocation and schedule of all 16
+// existing instantiations (docs/kernels.md "Residual dropout").
+//
+// Element (row, col) of the (M, N) branch is kept iff
+// Dropout::keep(row * N + col) holds (attn_common.h: the attention kernels'
+// hash), whatever NVEC, R or the grid; the backward regenerates the mask
+// from (p, seed) and nothing is stored. keep() first folds its 64-bit index
+// to lo ^ hi and reads nothing else of it, so the kernels make that fold
+// themselves. row * N is wave-uniform (scalar registers) and a multiple of
+// 8, a vector's column offset is a per-lane multiple of 8 below 2048: one
+// 32-bit add with carry per vector gives the fold of its element 0, and
+// element k has fold ^ k (k < 8 only touches the three zero bits of lo). No
+// 64-bit per-lane value exists.
+DEV_INLINE unsigned ln_drop_fold(unsigned long long row_base, unsigned off) {
+  const unsigned blo = (unsigned)row_base;
+  const unsigned lo = blo + off;
+  const unsigned hi = (unsigned)(row_base >> 32) + (lo < blo ? 1u : 0u);
+  return lo ^ hi;
+}
+
+// No packed fp32 math in the dropout kernels, as in the attention files.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LN_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define LN_NO_PK_F32
+#endif
+
+// Forward: ln_fwd_rowwave_kernel<bf16, true, NVEC, R> with
+// h = x + (keep ? res * inv_keep : 0), in fp32 and rounded to bf16 once.
+// Statistics over the rounded h, y, mean and rstd as there, in its order.
+template <int NVEC, int R>
+__global__ __launch_bounds__(LN_RW_BLOCK) LN_NO_PK_F32
+void ln_fwd_rowwave_drop_kernel(
+    const bf16* __restrict__ x, const bf16* __restrict__ res,
+    bf16* __restrict__ h, const bf16* __restrict__ w,
+    const bf16* __restrict__ b, bf16* __restrict__ y,
+    float* __restrict__ mean, float* __restrict__ rstd, int M, int N,
+    float eps, Dropout drop) {
+  using VT = Vec<bf16>;
+  typedef typename VT::V V;
+  constexpr int W = VT::W;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int g = __builtin_amdgcn_readfirstlane(
+      (int)(blockIdx.x * LN_RW_WAVES + threadIdx.x / WAVE));
+  const long long G = (long long)gridDim.x * LN_RW_WAVES;
+  const bool last_ok = (lane + (NVEC - 1) * WAVE) * W < N;
+  const unsigned voff = lane * W;
+  const V zero = {};
+  V wv[NVEC], bv[NVEC];
+#pragma unroll
+  for (int j = 0; j < NVEC; ++j) {
+    wv[j] = bv[j] = zero;
+    if (j < NVEC - 1 || last_ok) {
+      wv[j] = VT::load(w + voff + j * WAVE * W);
+      bv[j] = VT::load(b + voff + j * WAVE * W);
+    }
+  }
+  for (long long row0 = g; row0 < M; row0 += G * R) {
+    V xc[R][NVEC], rc[R][NVEC];
+    // every load of the batch is issued before the first reduction
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const long long row = row0 + r * G;
+#pragma unroll
+      for (int j = 0; j < NVEC; ++j) xc[r][j] = rc[r][j] = zero;
+      if (row < M) {
+#pragma unroll
+        for (int j = 0; j < NVEC; ++j) {
+          if (j < NVEC - 1 || last_ok) {
+            xc[r][j] = VT::load(x + row * N + voff + j * WAVE * W);
+            rc[r][j] = VT::load(res + row * N + voff + j * WAVE * W);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const long long row = row0 + r * G;
+      if (row < M) {
+        float ps[NVEC], pss[NVEC];
+#pragma unroll
+        for (int j = 0; j < NVEC; ++j) {
+          ps[j] = pss[j] = 0.f;
+          const unsigned fold =
+              ln_drop_fold((unsigned long long)row * N, voff + j * WAVE * W);
+          V hv;
+#pragma unroll
+          for (int k = 0; k < W; ++k) {
+            const float rk = drop.keep(fold ^ (unsigned)k)
+                                 ? VT::get(rc[r][j], k) * drop.inv_keep
+                                 : 0.f;
+            VT::set(hv, k, VT::get(xc[r][j], k) + rk);
+          }
+          if (j < NVEC - 1 || last_ok)
+            VT::store(h + row * N + voff + j * WAVE * W, hv);
+          xc[r][j] = hv;
+#pragma unroll
+          for (int k = 0; k < W; ++k) {
+            float f = VT::get(hv, k);
+            ps[j] += f;
+            pss[j] += f * f;
+          }
+        }
+        const float s = ln_rw_row_sum<NVEC>(ps);
+        const float ss = ln_rw_row_sum<NVEC>(pss);
+        const float mu = s / N;
+        const float var = fmaxf(ss / N - mu * mu, 0.0f);
+        const float rs = rsqrtf(var + eps);
+        if (lane == 0) {
+          mean[row] = mu;
+          rstd[row] = rs;
+        }
+#pragma unroll
+        for (int j = 0; j < NVEC; ++j) {
+          V ov;
+#pragma unroll
+          for (int k = 0; k < W; ++k) {
+            float xh = (VT::get(xc[r][j], k) - mu) * rs;
+            VT::set(ov, k, xh * VT::get(wv[j], k) + VT::get(bv[j], k));
+          }
+          if (j < NVEC - 1 || last_ok)
+            VT::store(y + row * N + voff + j * WAVE * W, ov);
+        }
+      }
+    }
+  }
+}
+
+// Backward: ln_bwd_rowwave_kernel<bf16, HAS_DH, NVEC, R> with a second
+// output, the gradient of the dropped branch: dres = keep ? gx * inv_keep : 0
+// from the fp32 gx (dh included) before dx rounds it. dx and the dw/db
+// stripes as there, in its order; `x` is the h the forward wrote.
+// Up to N = 1024 the kernel is compiled for four waves per SIMD: left alone
+// the HAS_DH form at NVEC = 2 takes 134 registers and a SIMD holds three;
+// capped it takes 128 and no scratch. The batch depth stays R = 2.
+template <bool HAS_DH, int NVEC, int R>
+__global__ __launch_bounds__(LN_RW_BLOCK) LN_NO_PK_F32
+__attribute__((amdgpu_waves_per_eu(NVEC <= 2 ? 4 : 1)))
+void ln_bwd_rowwave_drop_kernel(
+    const bf16* __restrict__ dy, const bf16* __restrict__ dh,
+    const bf16* __restrict__ x, const bf16* __restrict__ w,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    bf16* __restrict__ dx, bf16* __restrict__ dres, float* __restrict__ pdw,
+    float* __restrict__ pdb, int M, int N, Dropout drop) {
+  using VT = Vec<bf16>;
+  typedef typename VT::V V;
+  constexpr int W = VT::W;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int g = __builtin_amdgcn_readfirstlane(
+      (int)(blockIdx.x * LN_RW_WAVES + threadIdx.x / WAVE));
+  const long long G = (long long)gridDim.x * LN_RW_WAVES;
+  const bool last_ok = (lane + (NVEC - 1) * WAVE) * W < N;
+  const unsigned voff = lane * W;
+  const V zero = {};
+  V wv[NVEC];
+  float accdw[NVEC][W], accdb[NVEC][W];
+#pragma unroll
+  for (int j = 0; j < NVEC; ++j) {
+    wv[j] = zero;
+    if (j < NVEC - 1 || last_ok) wv[j] = VT::load(w + voff + j * WAVE * W);
+#pragma unroll
+    for (int k = 0; k < W; ++k) accdw[j][k] = accdb[j][k] = 0.f;
+  }
+  for (long long row0 = g; row0 < M; row0 += G * R) {
+    V dyc[R][NVEC], xc[R][NVEC];
+    float mu[R], rs[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const long long row = row0 + r * G;
+      mu[r] = rs[r] = 0.f;
+#pragma unroll
+      for (int j = 0; j < NVEC; ++j) dyc[r][j] = xc[r][j] = zero;
+      if (row < M) {
+        mu[r] = mean[row];
+        rs[r] = rstd[row];
+#pragma unroll
+        for (int j = 0; j < NVEC; ++j) {
+          if (j < NVEC - 1 || last_ok) {
+            dyc[r][j] = VT::load(dy + row * N + voff + j * WAVE * W);
+            xc[r][j] = VT::load(x + row * N + voff + j * WAVE * W);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const long long row = row0 + r * G;
+      if (row < M) {
+        float p1[NVEC], p2[NVEC];
+#pragma unroll
+        for (int j = 0; j < NVEC; ++j) {
+          p1[j] = p2[j] = 0.f;
+          // a lane without the last vector must not fold -mu*rs into dw
+          if (j < NVEC - 1 || last_ok) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+              float d = VT::get(dyc[r][j], k);
+              float xh = (VT::get(xc[r][j], k) - mu[r]) * rs[r];
+              float wdy = VT::get(wv[j], k) * d;
+              p1[j] += xh * wdy;
+              p2[j] += wdy;
+              accdw[j][k] += d * (VT::get(xc[r][j], k) - mu[r]) * rs[r];
+              accdb[j][k] += d;
+            }
+          }
+        }
+        // keep the row packed across the reduction (see the kernel above)
+#pragma unroll
+        for (int j = 0; j < NVEC; ++j)
+          asm volatile("" : "+v"(dyc[r][j]), "+v"(xc[r][j]));
+        V hc[NVEC];
+        if (HAS_DH) {
+#pragma unroll
+          for (int j = 0; j < NVEC; ++j) {
+            hc[j] = zero;
+            if (j < NVEC - 1 || last_ok)
+              hc[j] = VT::load(dh + row * N + voff + j * WAVE * W);
+          }
+        }
+        const float c1 = ln_rw_row_sum<NVEC>(p1) / N;
+        const float c2 = ln_rw_row_sum<NVEC>(p2) / N;
+#pragma unroll
+        for (int j = 0; j < NVEC; ++j) {
+          // one vector at a time: its hash values die with its two stores
+          const unsigned fold =
+              ln_drop_fold((unsigned long long)row * N, voff + j * WAVE * W);
+          V ov, rv;
+#pragma unroll
+          for (int k = 0; k < W; ++k) {
+            float d = VT::get(dyc[r][j], k);
+            float xh = (VT::get(xc[r][j], k) - mu[r]) * rs[r];
+            float wdy = VT::get(wv[j], k) * d;
+            float gx = (wdy - (xh * c1 + c2)) * rs[r];
+            if (HAS_DH) gx += VT::get(hc[j], k);
+            VT::set(ov, k, gx);
+            VT::set(rv, k,
+                    drop.keep(fold ^ (unsigned)k) ? gx * drop.inv_keep : 0.f);
+          }
+          if (j < NVEC - 1 || last_ok) {
+            VT::store(dx + row * N + voff + j * WAVE * W, ov);
+            VT::store(dres + row * N + voff + j * WAVE * W, rv);
+          }
+        }
+      }
+    }
+  }
+  float* sdw = pdw + (long long)g * N;
+  float* sdb = pdb + (long long)g * N;
+#pragma unroll
+  for (int j = 0; j < NVEC; ++j) {
+    if (j < NVEC - 1 || last_ok) {
+      const unsigned col = voff + j * WAVE * W;
+#pragma unroll
+      for (int k = 0; k < W; k += 4) {
+        f32x4 vw = {accdw[j][k], accdw[j][k + 1], accdw[j][k + 2],
+                    accdw[j][k + 3]};
+        f32x4 vb = {accdb[j][k], accdb[j][k + 1], accdb[j][k + 2],
+                    accdb[j][k + 3]};
+        *reinterpret_cast<f32x4*>(sdw + col + k) = vw;
+        *reinterpret_cast<f32x4*>(sdb + col + k) = vb;
+      }
+    }
+  }
+}
+
 // ---- wide-row backward -----------------------------------------------------
 // Rows beyond the register-cache bound (N > LN_WG_MAXITER * block * W) are a
 // correctness fallback for non-GPT widths; the forward is ln_fwd_kernel with
@@ -799,6 +1069,29 @@ hipError_t tdsa_ln_fwd(const void* x, const void* res, void* h, const void* w,
   });
 }
 
+// Residual dropout forward, routed shapes only (ln_rw_nvec): any other shape
+// is an error, there is no second path. Grid and depth are the plain
+// forward's.
+hipError_t tdsa_ln_drop_fwd(const void* x, const void* res, void* h,
+                            const void* w, const void* b, void* y, float* mean,
+                            float* rstd, int M, int N, float eps, float p,
+                            unsigned long long seed, int is_bf16,
+                            hipStream_t stream) {
+  const int nvec = ln_rw_nvec(N, is_bf16);
+  if (!nvec || !res || !h) return hipErrorInvalidValue;
+  const Dropout drop = make_dropout(p, seed);
+  const int grid = ln_rw_fwd_waves(M) / LN_RW_WAVES;
+  ln_rw_with_nvec(nvec, [&](auto nv) {
+    constexpr int NV = decltype(nv)::value;
+    hipLaunchKernelGGL(
+        (ln_fwd_rowwave_drop_kernel<NV, LN_RW_FWD_DEPTH(NV)>), dim3(grid),
+        dim3(LN_RW_BLOCK), 0, stream, (const bf16*)x, (const bf16*)res,
+        (bf16*)h, (const bf16*)w, (const bf16*)b, (bf16*)y, mean, rstd, M, N,
+        eps, drop);
+  });
+  return hipGetLastError();
+}
+
 // G (stripe count), reported to the caller so it can size pdw/pdb. This and
 // the launcher below both take it from ln_stripe_count, the single place that
 // decides it.
@@ -832,6 +1125,32 @@ hipError_t tdsa_ln_bwd_dx(const void* dy, const void* dh, const void* x,
     return ln_bwd_dx_wg((const T*)dy, (const T*)dh, (const T*)x, (const T*)w,
                         mean, rstd, (T*)dx, pdw, pdb, M, N, stream);
   });
+}
+
+// Residual dropout backward, routed shapes only: dx as tdsa_ln_bwd_dx plus
+// dres under the forward's mask. Stripes and grid are tdsa_ln_bwd_dx's.
+hipError_t tdsa_ln_drop_bwd_dx(const void* dy, const void* dh, const void* x,
+                               const void* w, const float* mean,
+                               const float* rstd, void* dx, void* dres,
+                               float* pdw, float* pdb, int M, int N, float p,
+                               unsigned long long seed, int is_bf16,
+                               hipStream_t stream) {
+  const int nvec = ln_rw_nvec(N, is_bf16);
+  if (!nvec || !dres) return hipErrorInvalidValue;
+  const Dropout drop = make_dropout(p, seed);
+  const int grid = ln_stripe_count(M, nvec) / LN_RW_WAVES;
+  ln_rw_with_nvec(nvec, [&](auto nv) {
+    ln_with_flag(dh != nullptr, [&](auto has_dh) {
+      constexpr int NV = decltype(nv)::value;
+      hipLaunchKernelGGL(
+          (ln_bwd_rowwave_drop_kernel<decltype(has_dh)::value, NV,
+                                      LN_RW_BWD_DEPTH(NV)>),
+          dim3(grid), dim3(LN_RW_BLOCK), 0, stream, (const bf16*)dy,
+          (const bf16*)dh, (const bf16*)x, (const bf16*)w, mean, rstd,
+          (bf16*)dx, (bf16*)dres, pdw, pdb, M, N, drop);
+    });
+  });
+  return hipGetLastError();
 }
 
 // out_bf16: write dw/db as bf16 (rounded once from the fp32 sums) instead

@@ -9,6 +9,10 @@ spread of the rounds is the noise a difference has to beat. The HIP
 candidates are called directly (no autotuner in between).
 
   python scripts/bench_ln.py [--rounds 5] [--M 32768] [--N 1024]
+
+--dropout P adds the residual-dropout pair, alternated per round with the
+plain fused pair and with what a user would write without it: F.dropout(res)
+in front of the fused forward and the mask multiply after the fused backward.
 """
 
 import argparse
@@ -44,6 +48,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--M", type=int, default=32768)
     ap.add_argument("--N", type=int, default=1024)
+    ap.add_argument("--dropout", type=float, default=0.0)
     args = ap.parse_args()
     M, N = args.M, args.N
     bf = torch.bfloat16
@@ -94,6 +99,51 @@ def main():
             print(f"{name:10s} ROWWAVE={knob}  median {med:6.1f} us  "
                   f"{rate:5.2f} TB/s ({100 * rate / gelu_rate:3.0f}% of gelu)  "
                   f"rounds: {rounds}")
+    if args.dropout > 0:
+        bench_dropout(args.rounds, args.dropout, x, res, w, b, dy, dh)
+
+
+def bench_dropout(rounds, p, x, res, w, b, dy, dh):
+    bf = x.dtype
+    seed = (1 << 40) + 12345
+    h, _, mean, rstd = L.layernorm_fwd_res_dropout(x, res, w, b, p, seed)
+    res_g = res.clone().requires_grad_(True)
+    dropped = torch.nn.functional.dropout(res_g, p, True)
+
+    def bwd_plain():
+        _, ws = L.ln_dx_hip(dy, h, w, mean, rstd, dh)
+        ops.layernorm_dwdb(ws, dtype=bf)
+
+    def bwd_drop():
+        _, _, ws = L.layernorm_dx_dropout(dy, h, w, mean, rstd, dh, p, seed)
+        ops.layernorm_dwdb(ws, dtype=bf)
+
+    def bwd_torch():
+        dx, ws = L.ln_dx_hip(dy, h, w, mean, rstd, dh)
+        ops.layernorm_dwdb(ws, dtype=bf)
+        torch.autograd.grad(dropped, res_g, dx, retain_graph=True)
+
+    parts = [
+        ("a fwd+res", lambda: L.ln_fwd_res_hip(x, res, w, b, 1e-5)),
+        ("b fwd+res+drop",
+         lambda: L.layernorm_fwd_res_dropout(x, res, w, b, p, seed)),
+        ("c F.dropout, fwd+res", lambda: L.ln_fwd_res_hip(
+            x, torch.nn.functional.dropout(res, p, True), w, b, 1e-5)),
+        ("a bwd full", bwd_plain),
+        ("b bwd full+drop", bwd_drop),
+        ("c bwd full, dropout bwd", bwd_torch),
+    ]
+    times = {name: [] for name, _ in parts}
+    for _ in range(rounds):
+        for name, fn in parts:
+            times[name].append(timeit(fn))
+    print(f"residual dropout p={p}: a = fused pair, b = dropout kernels, "
+          f"c = torch dropout around the fused pair")
+    for name, _ in parts:
+        ts = times[name]
+        rounds_s = " ".join(f"{t:6.1f}" for t in ts)
+        print(f"{name:24s} median {sorted(ts)[len(ts) // 2]:6.1f} us  "
+              f"range {min(ts):6.1f}-{max(ts):6.1f}  rounds: {rounds_s}")
 
 
 if __name__ == "__main__":

@@ -29,7 +29,13 @@ class GPTConfig:
     n_layer: int = 12
     n_head: int = 12
     n_embd: int = 768
+    # attention probabilities (fused into the attention kernels) and the
+    # embedding sum
     dropout: float = 0.0
+    # each block's two residual branches (after the attention and the MLP
+    # c_proj), fused into the next residual LayerNorm kernel: no extra pass,
+    # no stored mask
+    resid_dropout: float = 0.0
     bias: bool = False
     # "fused": CDNA4 flash-style kernel (composite torch on CPU);
     # "math": composite torch attention everywhere.
@@ -127,6 +133,14 @@ class Block(nn.Module):
         self.attn = CausalSelfAttention(config)
         self.ln_2 = nn.LayerNorm(config.n_embd)
         self.mlp = MLP(config)
+        self.resid_dropout = config.resid_dropout
+
+    def _drop(self, delta):
+        """Residual dropout on the raw nn.LayerNorm path."""
+        if self.resid_dropout > 0:
+            return nn.functional.dropout(delta, self.resid_dropout,
+                                         self.training)
+        return delta
 
     def forward(self, x, delta=None):
         """Residual stream threading: takes (x, pending delta) and returns
@@ -137,15 +151,15 @@ class Block(nn.Module):
             y1 = self.ln_1(x)
             h = x
         elif hasattr(self.ln_1, "forward_fused"):
-            h, y1 = self.ln_1.forward_fused(x, delta)
+            h, y1 = self.ln_1.forward_fused(x, delta, self.resid_dropout)
         else:
-            h = x + delta
+            h = x + self._drop(delta)
             y1 = self.ln_1(h)
         a = self.attn(y1)
         if hasattr(self.ln_2, "forward_fused"):
-            h2, y2 = self.ln_2.forward_fused(h, a)
+            h2, y2 = self.ln_2.forward_fused(h, a, self.resid_dropout)
         else:
-            h2 = h + a
+            h2 = h + self._drop(a)
             y2 = self.ln_2(h2)
         return h2, self.mlp(y2)
 
@@ -189,8 +203,11 @@ class GPT2Model(nn.Module):
         if delta is None:
             y = ln_f(x)
         elif hasattr(ln_f, "forward_fused"):
-            _, y = ln_f.forward_fused(x, delta)
+            _, y = ln_f.forward_fused(x, delta, self.config.resid_dropout)
         else:
+            if self.config.resid_dropout > 0:
+                delta = nn.functional.dropout(
+                    delta, self.config.resid_dropout, self.training)
             y = ln_f(x + delta)
         if (targets is not None and self.config.fused_lm_head
                 and hasattr(self.lm_head, "project_cross_entropy")):

@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..ops.attention import _draw_seed
 from .linear import _ParamHooks, _check_grad_shape
 
 
@@ -34,6 +35,31 @@ class _LayerNormResFn(torch.autograd.Function):
             return dh, dh, None, None, None
         dx, dw, db = ctx.module.backward_callback(dy, h, mean, rstd, dh=dh)
         return dx, dx, dw, db, None
+
+
+class _LayerNormResDropoutFn(torch.autograd.Function):
+    """_LayerNormResFn with dropout on the residual branch:
+    h = x + dropout(res, p). The mask is a function of (p, seed) alone
+    (ops.dropout_keep_mask); backward regenerates it, nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, x, res, weight, bias, module, p, seed):
+        ctx.module = module
+        ctx.dropout = (p, seed)
+        ctx.set_materialize_grads(False)
+        h, y, mean, rstd = module.forward_res_callback(x, res, (p, seed))
+        ctx.save_for_backward(h, mean, rstd)
+        return h, y
+
+    @staticmethod
+    def backward(ctx, dh, dy):
+        h, mean, rstd = ctx.saved_tensors
+        if dy is None:  # y unused: gradient flows through h alone
+            return (dh, ops.dropout_grad(dh, *ctx.dropout), None, None, None,
+                    None, None)
+        dx, dres, dw, db = ctx.module.backward_callback(
+            dy, h, mean, rstd, dh=dh, dropout=ctx.dropout)
+        return dx, dres, dw, db, None, None, None
 
 
 class _LayerNormFn(torch.autograd.Function):
@@ -75,15 +101,26 @@ class LayerNorm(_ParamHooks, nn.LayerNorm):
         weight, bias = self._params_fwd()
         return ops.layernorm_fwd(x, weight, bias, eps=self.eps, tuner=self.tuner)
 
-    def forward_res_callback(self, x, res):
+    def forward_res_callback(self, x, res, dropout=None):
+        """dropout: (p, seed) of the residual-branch dropout, or None."""
         weight, bias = self._params_fwd()
+        if dropout is not None:
+            return ops.layernorm_fwd_res_dropout(x, res, weight, bias,
+                                                 *dropout, eps=self.eps)
         return ops.layernorm_fwd_res(x, res, weight, bias, eps=self.eps,
                                      tuner=self.tuner)
 
-    def backward_callback(self, dy, x, mean, rstd, dh=None):
+    def backward_callback(self, dy, x, mean, rstd, dh=None, dropout=None):
+        """(dx, dw, db); with dropout = (p, seed), (dx, dres, dw, db)."""
         w = self._weight_bwd()
-        dx, ws = ops.layernorm_dx(dy, x, w, mean, rstd, dh=dh,
-                                  tuner=self.tuner)
+        dres = ()
+        if dropout is not None:
+            dx, dr, ws = ops.layernorm_dx_dropout(dy, x, w, mean, rstd, dh,
+                                                  *dropout)
+            dres = (dr,)
+        else:
+            dx, ws = ops.layernorm_dx(dy, x, w, mean, rstd, dh=dh,
+                                      tuner=self.tuner)
         dw = db = None
         if self.weight.requires_grad:
             dw, db = ops.layernorm_dwdb(ws, dtype=self.weight.dtype, tuner=self.tuner)
@@ -91,11 +128,18 @@ class LayerNorm(_ParamHooks, nn.LayerNorm):
             _check_grad_shape(self.bias, db)
             dw = self._publish(self.weight, dw)
             db = self._publish(self.bias, db)
-        return dx, dw, db
+        return (dx, *dres, dw, db)
 
     def forward(self, x):
         return _LayerNormFn.apply(x, self.weight, self.bias, self)
 
-    def forward_fused(self, x, res):
-        """(h, y) = (x + res, LN(x + res)) with the add fused in-kernel."""
+    def forward_fused(self, x, res, dropout_p=0.0):
+        """(h, y) = (x + res, LN(x + res)) with the add fused in-kernel.
+        In training mode dropout_p > 0 drops the residual branch first,
+        h = x + dropout(res, dropout_p), in the same kernel, with a fresh seed
+        from the torch CPU RNG as attention dropout draws it."""
+        if self.training and dropout_p > 0.0:
+            return _LayerNormResDropoutFn.apply(
+                x, res, self.weight, self.bias, self, dropout_p,
+                _draw_seed())
         return _LayerNormResFn.apply(x, res, self.weight, self.bias, self)

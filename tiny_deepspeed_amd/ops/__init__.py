@@ -13,7 +13,8 @@ from .linear import (
     linear_bias_grad,
 )
 from .layernorm import (layernorm_fwd, layernorm_fwd_res, layernorm_dx,
-                        layernorm_dwdb)
+                        layernorm_dwdb, layernorm_fwd_res_dropout,
+                        layernorm_dx_dropout, dropout_keep_mask, dropout_grad)
 from .embedding import embedding_forward, embedding_weight_grad
 from .gelu import gelu, gelu_fwd, gelu_bwd
 from .attention import causal_attention, fused_causal_attention
@@ -26,6 +27,8 @@ from .utils import acc_dtype
 __all__ = [
     "linear_forward", "linear_input_grad", "linear_weight_grad", "linear_bias_grad",
     "layernorm_fwd", "layernorm_fwd_res", "layernorm_dx", "layernorm_dwdb",
+    "layernorm_fwd_res_dropout", "layernorm_dx_dropout", "dropout_keep_mask",
+    "dropout_grad",
     "embedding_forward", "embedding_weight_grad",
     "gelu", "gelu_fwd", "gelu_bwd",
     "causal_attention", "fused_causal_attention",

@@ -122,3 +122,94 @@ def layernorm_dwdb(workspace, dtype=None, tuner=None):
     if dtype is not None:
         dw, db = dw.to(dtype), db.to(dtype)
     return dw, db
+
+
+# --- residual dropout ------------------------------------------------------
+# h = x + dropout(res, p) fused into the residual LayerNorm. Element
+# (row, col) of the (M, N) branch is kept iff the attention kernels' hash
+# (csrc/kernels/attn_common.h, Dropout::keep) of `seed` keeps index
+# row * N + col, and a kept element is scaled by 1 / (1 - p). The kernels
+# regenerate the mask in backward from (p, seed); nothing is stored.
+_M32 = 0xFFFFFFFF
+
+
+def _dropout_consts(p):
+    """(keep threshold, 1/(1-p) as fp32) exactly as make_dropout computes them
+    from the fp32 p the launcher receives."""
+    keep = 1.0 - torch.tensor(p, dtype=torch.float32).item()
+    thr = min(int(keep * 4294967296.0), _M32)
+    return thr, torch.tensor(1.0 / keep, dtype=torch.float32).item()
+
+
+def _keep_at(idx, p, seed):
+    """Dropout::keep at every index of the int64 tensor idx: int64 arithmetic
+    masked to 32 bits after every step."""
+    thr, _ = _dropout_consts(p)
+    h = (idx ^ (idx >> 32)) & _M32
+    h = (h + (seed & _M32)) & _M32
+    h = h ^ ((seed >> 32) & _M32)
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & _M32
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & _M32
+    h = h ^ (h >> 16)
+    return h < thr
+
+
+def dropout_keep_mask(M, N, p, seed, device=None):
+    """Bool (M, N) keep mask of the residual-dropout kernels, the torch
+    replica of Dropout::keep(row * N + col). One (M, N, p, seed) is one mask
+    on any device."""
+    row = torch.arange(M, dtype=torch.int64, device=device).unsqueeze(1)
+    col = torch.arange(N, dtype=torch.int64, device=device).unsqueeze(0)
+    return _keep_at(row * N + col, p, seed)
+
+
+def _dropout_routed(x):
+    """True where the dropout kernels run: GPU, and a shape on the
+    row-per-wave path (bf16, N % 8 == 0, N <= 2048, TDSA_LN_ROWWAVE on)."""
+    if not _ext.use_native(x) or x.dtype != torch.bfloat16:
+        return False
+    N = x.shape[-1]
+    geometry = _ext.get_ext().layernorm_rowwave_geometry(x.numel() // N, N, True)
+    return geometry[2] > 0
+
+
+def _mask_like(x, p, seed):
+    N = x.shape[-1]
+    return dropout_keep_mask(x.numel() // N, N, p, seed, x.device).view(x.shape)
+
+
+def layernorm_fwd_res_dropout(x, res, weight, bias, p, seed, eps=1e-5):
+    """h = x + dropout(res, p); y = LN(h). Returns (h, y, mean, rstd).
+    Routed GPU shapes run the kernel directly (a composite would only make
+    the same mask more slowly: nothing to tune); everything else builds the
+    mask with dropout_keep_mask and runs layernorm_fwd."""
+    if _dropout_routed(x):
+        y, mean, rstd, h = _ext.get_ext().layernorm_dropout_fwd(
+            x.contiguous(), res.contiguous(), weight, bias, eps, p, seed)
+        return h, y, mean, rstd
+    _, inv_keep = _dropout_consts(p)
+    kept = torch.where(_mask_like(x, p, seed), res.float() * inv_keep, 0.0)
+    h = (x.float() + kept).to(x.dtype)
+    y, mean, rstd = layernorm_fwd(h, weight, bias, eps)
+    return h, y, mean, rstd
+
+
+def layernorm_dx_dropout(dy, h, weight, mean, rstd, dh, p, seed):
+    """Backward of layernorm_fwd_res_dropout: (dx, dres, workspace), dx and
+    the workspace as layernorm_dx(dy, h, ..., dh) gives them and
+    dres = keep ? dx / (1 - p) : 0 under the forward's mask."""
+    if _dropout_routed(h):
+        dx, dres, pdw, pdb = _ext.get_ext().layernorm_dropout_bwd_dx(
+            dy.contiguous(), h.contiguous(), weight, mean, rstd, dh, p, seed)
+        return dx, dres, (pdw, pdb)
+    dx, ws = layernorm_dx(dy, h, weight, mean, rstd, dh=dh)
+    return dx, dropout_grad(dx, p, seed), ws
+
+
+def dropout_grad(g, p, seed):
+    """keep ? g / (1 - p) : 0 under the mask of (g's rows, p, seed)."""
+    _, inv_keep = _dropout_consts(p)
+    return torch.where(_mask_like(g, p, seed), g.float() * inv_keep,
+                       0.0).to(g.dtype)
