@@ -610,19 +610,42 @@ at::Tensor linear_dx_nt(at::Tensor dy2, at::Tensor w) {
 // ragged: the attention_ragged_* and attention_d128_ragged_* entry points,
 // any T >= 1.
 // D: the entry point's head dim (64; 128 for attention_d128_*).
-struct AttnTensor { const char* name; const at::Tensor &t, &lead; };
+// kv (the grouped-query entry points): a tensor of the K/V heads, (B,Hkv,T,D)
+// with Hkv dividing q's H; its `lead` is k for k/v and dk for dk/dv, which
+// holds the two to one Hkv and one stride group. op: named in every message.
+struct AttnTensor {
+  const char* name;
+  const at::Tensor &t, &lead;
+  bool kv = false;
+};
 static void check_attn_call(std::initializer_list<AttnTensor> tensors,
-                            double dropout_p, bool ragged, int64_t D = 64) {
+                            double dropout_p, bool ragged, int64_t D = 64,
+                            const char* op = nullptr) {
+  const std::string who = op ? std::string(op) + ": " : std::string();
   const at::Tensor& q = tensors.begin()->t;
-  for (const auto& [name, t, lead] : tensors) {
-    TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-    TORCH_CHECK(t.dim() == 4 && t.size(3) == D, name,
+  for (const auto& [name, t, lead, kv] : tensors) {
+    TORCH_CHECK(t.is_cuda(), who, name, " must be on GPU");
+    TORCH_CHECK(t.dim() == 4 && t.size(3) == D, who, name,
                 ": attention kernel requires (B,H,T,", D, ")");
-    TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
-    TORCH_CHECK(t.stride(3) == 1, name, " last dim must be contiguous");
-    TORCH_CHECK(t.sizes() == q.sizes(), name, " must have q's sizes ",
+    TORCH_CHECK(t.scalar_type() == at::kBFloat16, who, name, " must be bf16");
+    TORCH_CHECK(t.stride(3) == 1, who, name, " last dim must be contiguous");
+    if (kv) {
+      TORCH_CHECK(t.size(0) == q.size(0) && t.size(2) == q.size(2), who, name,
+                  " must be (B,Hkv,T,", D, ") with B and T of q ", q.sizes(),
+                  ", got ", t.sizes());
+      TORCH_CHECK(t.size(1) >= 1 && q.size(1) % t.size(1) == 0, who, name,
+                  " has ", t.size(1), " heads, which do not divide q's ",
+                  q.size(1));
+      TORCH_CHECK(t.sizes() == lead.sizes(), who, name,
+                  ": k/v and dk/dv must have one Hkv, got ", t.sizes(),
+                  " against ", lead.sizes());
+      TORCH_CHECK(t.strides() == lead.strides(), who, name,
+                  ": k/v and dk/dv must each share strides");
+      continue;
+    }
+    TORCH_CHECK(t.sizes() == q.sizes(), who, name, " must have q's sizes ",
                 q.sizes(), ", got ", t.sizes());
-    TORCH_CHECK(t.strides() == lead.strides(), name,
+    TORCH_CHECK(t.strides() == lead.strides(), who, name,
                 ": q/k/v, o/dout and dq/dk/dv must each share strides");
   }
   if (ragged) {
@@ -805,6 +828,59 @@ std::vector<at::Tensor> attention_d128_ragged_bwd(
                             seed);
 }
 
+// Grouped-query attention at head dim 128 (the attn_d128_gqa_* kernels): k, v
+// (and dk, dv) are (B, Hkv, T, 128) with Hkv dividing q's H; any T >= 1, no
+// dropout. lse is (B, H, T).
+std::vector<at::Tensor> attention_d128_gqa_fwd(at::Tensor q, at::Tensor k,
+                                               at::Tensor v, double scale,
+                                               c10::optional<at::Tensor> out) {
+  const char* op = "attention_d128_gqa_fwd";
+  at::Tensor o = out.has_value() ? *out : at::empty_like(q);
+  check_attn_call({{"q", q, q}, {"k", k, k, true}, {"v", v, k, true},
+                   {"out", o, o}}, 0.0, true, 128, op);
+  const long long B = q.size(0), H = q.size(1), T = q.size(2);
+  auto lse = at::empty({B, H, T}, q.options().dtype(at::kFloat));
+  check_hip(tdsa_attn_d128_gqa_fwd(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                lse.data_ptr<float>(), B, H, k.size(1), (int)T, (float)scale,
+                strides3(q).data(), strides3(k).data(), strides3(o).data(),
+                cur_stream()),
+            op);
+  return {o, lse};
+}
+
+std::vector<at::Tensor> attention_d128_gqa_bwd(
+    at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
+    at::Tensor dout, double scale, c10::optional<at::Tensor> dq_out,
+    c10::optional<at::Tensor> dk_out, c10::optional<at::Tensor> dv_out) {
+  const char* op = "attention_d128_gqa_bwd";
+  at::Tensor dq = dq_out.has_value() ? *dq_out : at::empty_like(q);
+  at::Tensor dk = dk_out.has_value() ? *dk_out : at::empty_like(k);
+  at::Tensor dv = dv_out.has_value() ? *dv_out : at::empty_like(v);
+  check_attn_call({{"q", q, q}, {"k", k, k, true}, {"v", v, k, true},
+                   {"o", o, o}, {"dout", dout, o}, {"dq", dq, dq},
+                   {"dk", dk, dk, true}, {"dv", dv, dk, true}},
+                  0.0, true, 128, op);
+  TORCH_CHECK(dk.size(1) == k.size(1), op, ": dk must have k's sizes ",
+              k.sizes(), ", got ", dk.sizes());
+  const long long B = q.size(0), H = q.size(1), T = q.size(2);
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
+                  lse.numel() == B * H * T,
+              op, ": lse must be fp32 on GPU with B*H*T elements, got ",
+              lse.sizes());
+  auto lsec = lse.contiguous();
+  auto delta = at::empty({B, H, T}, q.options().dtype(at::kFloat));
+  check_hip(tdsa_attn_d128_gqa_bwd(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                lsec.data_ptr<float>(), dout.data_ptr(), dq.data_ptr(),
+                dk.data_ptr(), dv.data_ptr(), delta.data_ptr<float>(), B, H,
+                k.size(1), (int)T, (float)scale, strides3(q).data(),
+                strides3(k).data(), strides3(o).data(), strides3(dq).data(),
+                strides3(dk).data(), cur_stream()),
+            op);
+  return {dq, dk, dv};
+}
+
 // ---- debug probes ---------------------------------------------------------
 at::Tensor dbg_mfma(at::Tensor A, at::Tensor B, int64_t variant) {
   check_call("dbg_mfma", {{"A", A, at::kBFloat16, 16 * 32},
@@ -916,6 +992,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("dq") = py::none(), py::arg("dk") = py::none(),
           py::arg("dv") = py::none(), py::arg("dropout_p") = 0.0,
           py::arg("seed") = 0);
+  mod.def("attention_d128_gqa_fwd", &attention_d128_gqa_fwd, py::arg("q"),
+          py::arg("k"), py::arg("v"), py::arg("scale"),
+          py::arg("out") = py::none());
+  mod.def("attention_d128_gqa_bwd", &attention_d128_gqa_bwd, py::arg("q"),
+          py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"),
+          py::arg("dout"), py::arg("scale"), py::arg("dq") = py::none(),
+          py::arg("dk") = py::none(), py::arg("dv") = py::none());
   mod.def("attention_ragged_fwd", &attention_ragged_fwd, py::arg("q"),
           py::arg("k"), py::arg("v"), py::arg("scale"),
           py::arg("out") = py::none(), py::arg("dropout_p") = 0.0,

@@ -3,6 +3,8 @@
 // variants ("Ragged T" above the first tail kernel), which handle the partial
 // last tile and read or write no row >= T. With dropout either runs as its
 // DROP instantiation ("Dropout" above the first of those kernels).
+// k and v with fewer heads than q run the grouped-query kernels
+// ("Grouped-query" above them; no dropout).
 //
 // Same scheme and number formats as attention.hip (head dim 64): forward with
 // online softmax in exp2 space and a natural-log lse; backward in two kernels
@@ -239,6 +241,19 @@ DEV_INLINE void store_ctiles128(bf16* p, int st, const BlockCtx& c,
 // allocation of the forward and dkv kernels without dropout.
 DEV_INLINE const Dropout& the_dropout(const Dropout& d) { return d; }
 
+// Grouped-query attention ("Grouped-query" above the GQA kernels) rides in
+// the same pack: one KvHeads in the GQA kernels, which have no DROP form.
+// G = H / Hkv query heads share K/V head h / G, so the K/V head of query
+// (batch, head) bh is bh / G of B * Hkv, addressed through k's and v's own
+// strides sk.
+struct KvHeads {
+  int G, Hkv;
+  GStride sk;
+};
+DEV_INLINE const KvHeads& the_kv_heads(const KvHeads& h) { return h; }
+template <typename T, typename... Pack>
+constexpr bool pack_has = (std::is_same_v<T, Pack> || ...);
+
 // Waves per SIMD that the forward and dq kernels are compiled for. 2 holds
 // the 4-wave kernels to 256 registers (left alone the compiler takes 316 and
 // 344 of the 512 a lone wave may have, and a CU then holds one block, not
@@ -259,7 +274,8 @@ DEV_INLINE void d128_fwd_tile(const BlockCtx& c, char* smem,
                               bf16* __restrict__ o, float* __restrict__ lse,
                               int T, int H, float scale, const GStride& sq,
                               const GStride& so, const Drop&... drop_arg) {
-  constexpr bool DROP = sizeof...(Drop) != 0;
+  constexpr bool DROP = pack_has<Dropout, Drop...>;
+  constexpr bool GQA = pack_has<KvHeads, Drop...>;
   constexpr int BM = NW * 32;
   constexpr int NT = NW * WAVE;
   char* lds_k = smem;
@@ -272,8 +288,18 @@ DEV_INLINE void d128_fwd_tile(const BlockCtx& c, char* smem,
   unsigned long long drop_base = 0;
   if constexpr (DROP) drop_base = ((unsigned long long)c.bh * T + row_me) * T;
 
-  auto pipe_k = tile128_pipe<NT, TAIL>(k + boff, sq.t, c.tid, T);
-  auto pipe_v = tile128_pipe<NT, TAIL>(v + boff, sq.t, c.tid, T);
+  // K and V of this block's head; GQA: of K/V head bh / G, through sk
+  long long koff = boff;
+  int kst = sq.t;
+  if constexpr (GQA) {
+    const KvHeads& kvh = the_kv_heads(drop_arg...);
+    const int kvbh = (int)c.bh / kvh.G;   // B * H fits an int: grid y
+    koff = (long long)(kvbh / kvh.Hkv) * kvh.sk.b +
+           (long long)(kvbh % kvh.Hkv) * kvh.sk.h;
+    kst = kvh.sk.t;
+  }
+  auto pipe_k = tile128_pipe<NT, TAIL>(k + koff, kst, c.tid, T);
+  auto pipe_v = tile128_pipe<NT, TAIL>(v + koff, kst, c.tid, T);
   const FragOff kf(c);
   int trb[2][2];
   tr_bases(c.lane, trb);
@@ -457,7 +483,8 @@ DEV_INLINE void d128_bwd_dq_tile(const BlockCtx& c, char* smem,
                                  float scale, const GStride& sq,
                                  const GStride& so, const GStride& sd,
                                  const Drop&... drop_arg) {
-  constexpr bool DROP = sizeof...(Drop) != 0;
+  constexpr bool DROP = pack_has<Dropout, Drop...>;
+  constexpr bool GQA = pack_has<KvHeads, Drop...>;
   constexpr int BM = NW * 32;
   constexpr int NT = NW * WAVE;
   char* lds_k = smem;
@@ -474,8 +501,18 @@ DEV_INLINE void d128_bwd_dq_tile(const BlockCtx& c, char* smem,
   unsigned long long drop_base = 0;
   if constexpr (DROP) drop_base = ((unsigned long long)c.bh * T + row_me) * T;
 
-  auto pipe_k = tile128_pipe<NT, TAIL>(k + boff, sq.t, c.tid, T);
-  auto pipe_v = tile128_pipe<NT, TAIL>(v + boff, sq.t, c.tid, T);
+  // K and V of this block's head; GQA: of K/V head bh / G, through sk
+  long long koff = boff;
+  int kst = sq.t;
+  if constexpr (GQA) {
+    const KvHeads& kvh = the_kv_heads(drop_arg...);
+    const int kvbh = (int)c.bh / kvh.G;   // B * H fits an int: grid y
+    koff = (long long)(kvbh / kvh.Hkv) * kvh.sk.b +
+           (long long)(kvbh % kvh.Hkv) * kvh.sk.h;
+    kst = kvh.sk.t;
+  }
+  auto pipe_k = tile128_pipe<NT, TAIL>(k + koff, kst, c.tid, T);
+  auto pipe_v = tile128_pipe<NT, TAIL>(v + koff, kst, c.tid, T);
   const FragOff fo(c);
   int trb[2][2];
   tr_bases(c.lane, trb);
@@ -913,6 +950,311 @@ __global__ void attn_d128_bwd_dkv_drop_kernel(
   } while (c.next_pass());
 }
 
+// ---------------------------------------------------------------------------
+// Grouped-query: q, o, dout, dq, lse and delta have H heads, k, v, dk and dv
+// Hkv of them (H % Hkv == 0, G = H / Hkv), and query head h attends K/V head
+// h / G. k and v share the strides sk, dk and dv sdk. No DROP form.
+//   fwd, dq: the kernels above with a KvHeads in the pack: grid (tile, B*H),
+//        the same arithmetic per query head in the same order, only the K/V
+//        tiles come from head bh / G. o, lse, dq and delta carry the bits of
+//        the multi-head kernels on K/V expanded G-fold.
+//        The G heads of a group stream the same K/V, so the remapped y index
+//        is decoded group-minor (gqa_query_head): where B*Hkv % 8 == 0 they
+//        then share an XCD and its L2, as one head's blocks do.
+//   dkv: grid (tile or pair, B*Hkv); a workgroup owns NW*32 keys of a K/V
+//        head, loads them once and keeps dK/dV in registers while it walks
+//        the Q/dO tiles i0..n_q-1 of all G query heads of the group in ONE
+//        loop of G*(n_q-i0) iterations: the step from a head's last tile to
+//        the next head's first is an advance() by another uniform amount, so
+//        the pipeline never drains. One epilogue and one rounding per group:
+//        the group's sum is fp32 in the accumulators, in head order.
+// TAIL: the rules of "Ragged T" hold per query head: every head's last tile
+// takes the predicated fetch, and the pipes' row counts start over with each
+// head.
+// ---------------------------------------------------------------------------
+// The query (batch, head) of remapped y index y: group-minor with xcd_group,
+// so that y % 8, the XCD under xcd_remap, is the group's where B*Hkv % 8 == 0;
+// else y itself. Both are bijections of [0, B*H).
+DEV_INLINE int gqa_query_head(int y, int BH, int G, int xcd_group) {
+  if (!xcd_group) return y;
+  const int groups = BH / G;   // B * Hkv
+  return (y % groups) * G + y / groups;
+}
+
+template <int NW, bool TAIL>
+__launch_bounds__(NW * WAVE, fwd_dq_waves_per_simd(NW))
+NO_PK_F32
+__global__ void attn_d128_gqa_fwd_kernel(const bf16* __restrict__ q,
+                                         const bf16* __restrict__ k,
+                                         const bf16* __restrict__ v,
+                                         bf16* __restrict__ o,
+                                         float* __restrict__ lse, int T, int H,
+                                         int Hkv, float scale, GStride sq,
+                                         GStride sk, GStride so,
+                                         int xcd_group, int balance) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * TILE128];
+  BlockCtx c((T + NW * 32 - 1) / (NW * 32), balance, true);
+  const KvHeads kvh = {H / Hkv, Hkv, sk};
+  c.bh = gqa_query_head((int)c.bh, gridDim.y, kvh.G, xcd_group);
+  do {
+    d128_fwd_tile<NW, TAIL>(c, smem, q, k, v, o, lse, T, H, scale, sq, so,
+                            kvh);
+  } while (c.next_pass());
+}
+
+template <int NW, bool TAIL>
+__launch_bounds__(NW * WAVE, fwd_dq_waves_per_simd(NW))
+NO_PK_F32
+__global__ void attn_d128_gqa_bwd_dq_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k,
+    const bf16* __restrict__ v, const bf16* __restrict__ o,
+    const bf16* __restrict__ dout, const float* __restrict__ lse,
+    float* __restrict__ delta, bf16* __restrict__ dq, int T, int H, int Hkv,
+    float scale, GStride sq, GStride sk, GStride so, GStride sd,
+    int xcd_group, int balance) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * TILE128];
+  BlockCtx c((T + NW * 32 - 1) / (NW * 32), balance, true);
+  const KvHeads kvh = {H / Hkv, Hkv, sk};
+  c.bh = gqa_query_head((int)c.bh, gridDim.y, kvh.G, xcd_group);
+  do {
+    d128_bwd_dq_tile<NW, TAIL>(c, smem, q, k, v, o, dout, lse, delta, dq, T,
+                               H, scale, sq, so, sd, kvh);
+  } while (c.next_pass());
+}
+
+// next_tiles128 for the dkv loop over the heads of a group. With `wrap` the
+// pending tiles were a head's last, and the following ones are the first of
+// the next head: the pipes move by jump_x / jump_y elements and the rows by
+// row_jump instead of one tile, and every row count (TAIL) starts over at
+// left0. `wrap` is block-uniform.
+template <int NT, bool TAIL>
+DEV_INLINE void next_tiles128_heads(TilePipe<NT, TAIL>& x, char* lds_x,
+                                    TilePipe<NT, TAIL>& y, char* lds_y,
+                                    RowPipe<TAIL>& rows, bool more, bool wrap,
+                                    long long jump_x, long long jump_y,
+                                    long long row_jump, int left0) {
+  __syncthreads();
+  x.a.put(lds_x, x.pend_a);
+  x.b.put(lds_x + IMG, x.pend_b);
+  y.a.put(lds_y, y.pend_a);
+  y.b.put(lds_y + IMG, y.pend_b);
+  rows.put();
+  if (more) {
+    if (wrap) {
+#pragma unroll
+      for (int rep = 0; rep < Stage<NT>::REPS; ++rep) {
+        x.a.src[rep] += jump_x;
+        x.b.src[rep] += jump_x;
+        y.a.src[rep] += jump_y;
+        y.b.src[rep] += jump_y;
+      }
+      rows.ga += row_jump;
+      rows.gb += row_jump;
+      if constexpr (TAIL) {
+        x.left = left0;
+        y.left = left0;
+        rows.left = left0;
+      }
+    } else {
+      x.a.advance();
+      x.b.advance();
+      y.a.advance();
+      y.b.advance();
+      rows.advance();
+      if constexpr (TAIL) {
+        x.left -= KVB;
+        y.left -= KVB;
+      }
+    }
+    x.fetch();
+    y.fetch();
+    rows.fetch();
+  }
+}
+
+// K and V of the block's keys in LDS (the 2-wave kernel always; the 4-wave
+// kernel where GQA_DKV4_PINNED is false), as in d128_bwd_dkv_tile.
+constexpr bool GQA_DKV4_PINNED = true;
+
+template <int NW, bool TAIL>
+DEV_INLINE void d128_gqa_bwd_dkv_tile(
+    const BlockCtx& c, char* smem, const bf16* __restrict__ q,
+    const bf16* __restrict__ k, const bf16* __restrict__ v,
+    const bf16* __restrict__ dout, const float* __restrict__ lse,
+    const float* __restrict__ delta, bf16* __restrict__ dk,
+    bf16* __restrict__ dv, int T, int H, int Hkv, float scale,
+    const GStride& sq, const GStride& sk, const GStride& so,
+    const GStride& sdk) {
+  constexpr int BK = NW * 32;
+  constexpr int NT = NW * WAVE;
+  char* lds_q = smem;
+  char* lds_do = smem + TILE128;
+  float* lds_lse = reinterpret_cast<float*>(smem + 2 * TILE128);
+  float* lds_dlt = lds_lse + KVB;
+
+  // c.bh is the K/V head; its query heads are qbh .. qbh + G - 1, all of
+  // one batch, a head stride apart in q and dout and T apart in lse and delta
+  // (B * H fits an int, the grid's y: 32-bit divisions)
+  const int G = H / Hkv;
+  const int qbh = (int)c.bh * G;
+  auto head_off = [](int bh, int heads, const GStride& s) {
+    return (long long)(bh / heads) * s.b + (long long)(bh % heads) * s.h;
+  };
+  const long long koff = head_off((int)c.bh, Hkv, sk);
+  const int i0 = c.tile * BK / KVB;   // first Q tile that sees these keys
+  const int n_q = TAIL ? (T + KVB - 1) / KVB : T / KVB;   // Q tiles per head
+  const int left0 = T - i0 * KVB;
+  // from a head's last tile to the next head's tile i0
+  const long long back = (long long)(n_q - 1 - i0) * KVB;
+  const long long jump_q = sq.h - back * sq.t;
+  const long long jump_do = so.h - back * so.t;
+  const long long jump_row = T - back;
+
+  auto pipe_q = tile128_pipe<NT, TAIL>(
+      q + head_off(qbh, H, sq) + (long long)(i0 * KVB) * sq.t, sq.t, c.tid,
+      left0);
+  auto pipe_do = tile128_pipe<NT, TAIL>(
+      dout + head_off(qbh, H, so) + (long long)(i0 * KVB) * so.t, so.t, c.tid,
+      left0);
+  const FragOff af(c);
+  int trb[2][2];
+  tr_bases(c.lane, trb);
+  const int key_lo = c.tile * BK + c.w * 32;
+  const int key_me = key_lo + c.x32;
+  constexpr bool PINNED = (NW != 2) && GQA_DKV4_PINNED;
+  constexpr int OWN = BK / KVB;   // tiles of the block's own K (and V)
+  char* lds_kown = smem + 2 * TILE128 + 2 * KVB * 4;
+  char* lds_vown = lds_kown + OWN * TILE128;
+  bfrag k_frag[8], v_frag[8];
+  if constexpr (PINNED) {
+    load_row_frags_scaled<TAIL>(k_frag, k + koff, key_me, c.h32, sk.t,
+                                scale * LOG2E, key_me < T);
+    load_row_frags<TAIL>(v_frag, v + koff, key_me, c.h32, sk.t, key_me < T);
+  } else {
+    const long long kown = koff + (long long)(c.tile * BK) * sk.t;
+    __syncthreads();   // BAL_PAIRS: the previous pass has read its K and V
+#pragma unroll
+    for (int t = 0; t < OWN; ++t) {
+      // TAIL: T rounded up to 64 is a multiple of BK, so every tile of the
+      // block has at least one row
+      const long long kt = kown + (long long)(t * KVB) * sk.t;
+      stage_tile128_scaled<NT, TAIL>(lds_kown + t * TILE128, k + kt, sk.t,
+                                     c.tid, scale * LOG2E,
+                                     T - c.tile * BK - t * KVB);
+      stage_tile128_scaled<NT, TAIL>(lds_vown + t * TILE128, v + kt, sk.t,
+                                     c.tid, 1.0f, T - c.tile * BK - t * KVB);
+    }
+    // published by the barriers of the first loop iteration
+  }
+
+  const f32x16 kzero = {};
+  f32x16 dk_acc[4] = {};
+  f32x16 dv_acc[4] = {};
+
+  const long long row0 = (long long)qbh * T + i0 * KVB;
+  RowPipe<TAIL> rows(lse + row0, delta + row0, lds_lse, lds_dlt, LOG2E, c.tid,
+                     left0);
+  pipe_q.prime();
+  pipe_do.prime();
+  rows.fetch();
+  const int n_iter = G * (n_q - i0);
+  int i = i0;   // the Q tile of this iteration, i0..n_q-1 in every head
+  for (int it = 0; it < n_iter; ++it) {
+    const bool wrap = i + 1 == n_q;
+    next_tiles128_heads(pipe_q, lds_q, pipe_do, lds_do, rows,
+                        it + 1 < n_iter, wrap, jump_q, jump_do, jump_row,
+                        left0);
+    __syncthreads();
+
+    const int q0 = i * KVB;
+    i = wrap ? i0 : i + 1;
+    if (q0 + KVB - 1 < key_lo) continue;
+    if constexpr (TAIL) {
+      if (key_lo >= T) continue;   // a wave of padded keys only
+    }
+
+    const bool diag = q0 < key_lo + 32;
+    const int mask_lo = key_me - q0 - 4 * c.h32;   // diagonal tiles only
+    PackedC P, dS;
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2) {
+      // S, dP tiles: C[qrow = 32*t2 + crow(r,h32)][key = x32]
+      __builtin_amdgcn_s_setprio(1);
+      f32x16 s_acc, dp_acc;
+      if constexpr (PINNED) {
+        s_acc = mfma_rows_d128(lds_q, af, t2, k_frag, kzero);
+        dp_acc = mfma_rows_d128(lds_do, af, t2, v_frag, kzero);
+      } else {
+        s_acc = mfma_rows_d128<OWN>(lds_q, af, t2, lds_kown, c.w, kzero);
+        dp_acc = mfma_rows_d128<OWN>(lds_do, af, t2, lds_vown, c.w, kzero);
+      }
+      __builtin_amdgcn_s_setprio(0);
+      auto consume = [&](auto MASK) {
+#pragma unroll
+        for (int r1 = 0; r1 < 4; ++r1) {
+          float p[4], dsv[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = 4 * r1 + e;
+            const int lrow = t2 * 32 + crow(r, c.h32);
+            float pp = fast_exp2(s_acc[r] - lds_lse[lrow]);
+            // key_me <= q0 + lrow, the lane's part of lrow moved to mask_lo
+            if (MASK.value) pp = (t2 * 32 + crow(r, 0) >= mask_lo) ? pp : 0.f;
+            p[e] = pp;
+            dsv[e] = pp * (dp_acc[r] - lds_dlt[lrow]);   // scale in epilogue
+          }
+          P.wA[t2][r1] = pack2(p[0], p[1]);
+          P.wB[t2][r1] = pack2(p[2], p[3]);
+          dS.wA[t2][r1] = pack2(dsv[0], dsv[1]);
+          dS.wB[t2][r1] = pack2(dsv[2], dsv[3]);
+        }
+      };
+      if (diag)
+        consume(std::true_type{});
+      else
+        consume(std::false_type{});
+      // dV[key][d] += P^T dO ; dK[key][d] += dS^T Q over this half's rows
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int s = 2 * t2; s < 2 * t2 + 2; ++s) {
+        mfma_cols_d128(dv_acc, frag_from_packed(P, s), lds_do, trb, s);
+        mfma_cols_d128(dk_acc, frag_from_packed(dS, s), lds_q, trb, s);
+      }
+      __builtin_amdgcn_s_setprio(0);
+    }
+  }
+
+  __syncthreads();   // Q/dO tiles are consumed: their space holds the images
+  const BlockCtx e = c.fresh_lane();
+  const int ekey_lo = e.tile * BK + e.w * 32;
+  const long long doff =
+      head_off((int)e.bh, Hkv, sdk) + (long long)ekey_lo * sdk.t;
+  char* stage = smem + e.w * STAGE128;
+  store_ctiles128<TAIL>(dk + doff, sdk.t, e, dk_acc,
+                        [&](int) { return scale; }, stage, T - ekey_lo);
+  store_ctiles128<TAIL>(dv + doff, sdk.t, e, dv_acc,
+                        [&](int) { return 1.0f; }, stage, T - ekey_lo);
+}
+
+template <int NW, bool TAIL>
+__launch_bounds__(NW * WAVE)
+NO_PK_F32
+__global__ void attn_d128_gqa_bwd_dkv_kernel(
+    const bf16* __restrict__ q, const bf16* __restrict__ k,
+    const bf16* __restrict__ v, const bf16* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    bf16* __restrict__ dk, bf16* __restrict__ dv, int T, int H, int Hkv,
+    float scale, GStride sq, GStride sk, GStride so, GStride sdk,
+    int balance) {
+  __shared__ __attribute__((aligned(16)))
+  char smem[dkv_lds_bytes(NW, !GQA_DKV4_PINNED)];
+  BlockCtx c((T + NW * 32 - 1) / (NW * 32), balance, false);
+  do {
+    d128_gqa_bwd_dkv_tile<NW, TAIL>(c, smem, q, k, v, dout, lse, delta, dk,
+                                    dv, T, H, Hkv, scale, sq, sk, so, sdk);
+  } while (c.next_pass());
+}
+
 // Calls f(NW, TAIL, DROP) as std::integral_constants. TAIL: T % 64 != 0.
 // 4-wave blocks where 128 divides T rounded up to 64, else 2-wave blocks.
 template <typename F>
@@ -1021,6 +1363,15 @@ static hipError_t d128_launch_bwd(const void* q, const void* k, const void* v,
   return hipGetLastError();
 }
 
+// TDSA_ATTN_GQA_XCD, read at every launch: 1 (default) decodes the forward's
+// and dq's y index group-minor (gqa_query_head), 0 leaves it as it is
+// (profiles/attn_d128_gqa.txt has both timed).
+static int gqa_xcd_group() { return env_int("TDSA_ATTN_GQA_XCD", 1) != 0; }
+
+static bool gqa_heads_ok(long long H, long long Hkv) {
+  return Hkv >= 1 && H >= Hkv && H % Hkv == 0;
+}
+
 }  // namespace tdsa
 
 using namespace tdsa;
@@ -1074,6 +1425,67 @@ hipError_t tdsa_attn_d128_ragged_bwd(const void* q, const void* k,
   if (T < 1) return hipErrorInvalidValue;
   return d128_launch_bwd(q, k, v, o, lse, dout, dq, dk, dv, delta, B, H, T,
                          scale, sq, so, sd, dropout_p, seed, stream);
+}
+
+hipError_t tdsa_attn_d128_gqa_fwd(const void* q, const void* k, const void* v,
+                                  void* o, float* lse, long long B,
+                                  long long H, long long Hkv, int T,
+                                  float scale, const long long* sq_in,
+                                  const long long* sk_in,
+                                  const long long* so_in,
+                                  hipStream_t stream) {
+  if (T < 1 || !gqa_heads_ok(H, Hkv)) return hipErrorInvalidValue;
+  const GStride sq = gstride(sq_in), sk = gstride(sk_in), so = gstride(so_in);
+  d128_dispatch(T, false, [&](auto nw, auto tl, auto) {
+    constexpr int NW = decltype(nw)::value;
+    constexpr auto fwd = attn_d128_gqa_fwd_kernel<NW, decltype(tl)::value>;
+    const int n_tiles = (T + NW * 32 - 1) / (NW * 32);
+    const TileMap m = tile_map<fwd>(n_tiles, B * H, NW * WAVE);
+    hipLaunchKernelGGL(fwd, m.grid, dim3(NW * WAVE), 0, stream,
+                       (const bf16*)q, (const bf16*)k, (const bf16*)v,
+                       (bf16*)o, lse, T, (int)H, (int)Hkv, scale, sq, sk, so,
+                       gqa_xcd_group(), m.balance);
+  });
+  return hipGetLastError();
+}
+
+hipError_t tdsa_attn_d128_gqa_bwd(const void* q, const void* k, const void* v,
+                                  const void* o, const float* lse,
+                                  const void* dout, void* dq, void* dk,
+                                  void* dv, float* delta, long long B,
+                                  long long H, long long Hkv, int T,
+                                  float scale, const long long* sq_in,
+                                  const long long* sk_in,
+                                  const long long* so_in,
+                                  const long long* sd_in,
+                                  const long long* sdk_in,
+                                  hipStream_t stream) {
+  if (T < 1 || !gqa_heads_ok(H, Hkv)) return hipErrorInvalidValue;
+  const GStride sq = gstride(sq_in), sk = gstride(sk_in), so = gstride(so_in),
+                sd = gstride(sd_in), sdk = gstride(sdk_in);
+  // dq runs FIRST: it publishes delta, which dkv (same stream) consumes
+  d128_dispatch(T, false, [&](auto nw, auto tl, auto) {
+    constexpr int NW = decltype(nw)::value;
+    constexpr bool TAIL = decltype(tl)::value;
+    constexpr auto dq_k = attn_d128_gqa_bwd_dq_kernel<NW, TAIL>;
+    constexpr auto dkv_k = attn_d128_gqa_bwd_dkv_kernel<NW, TAIL>;
+    const int n_tiles = (T + NW * 32 - 1) / (NW * 32);
+    // dq maps the B*H query heads, dkv the B*Hkv K/V heads, whose workgroups
+    // cost G times as much: each mapping from its own grid and residency
+    const TileMap mq = tile_map<dq_k>(n_tiles, B * H, NW * WAVE);
+    const TileMap mkv = tile_map<dkv_k>(n_tiles, B * Hkv, NW * WAVE);
+    hipLaunchKernelGGL(dq_k, mq.grid, dim3(NW * WAVE), 0, stream,
+                       (const bf16*)q, (const bf16*)k, (const bf16*)v,
+                       (const bf16*)o, (const bf16*)dout, lse, delta,
+                       (bf16*)dq, T, (int)H, (int)Hkv, scale, sq, sk, so, sd,
+                       gqa_xcd_group(), mq.balance);
+    hipLaunchKernelGGL(dkv_k, mkv.grid, dim3(NW * WAVE), 0, stream,
+                       (const bf16*)q, (const bf16*)k, (const bf16*)v,
+                       (const bf16*)dout, lse, (const float*)delta,
+                       (bf16*)dk, (bf16*)dv, T, (int)H, (int)Hkv, scale, sq,
+                       sk, so, sdk, mkv.balance);
+  });
+  return hipGetLastError();
 }
 
 }  // extern "C"

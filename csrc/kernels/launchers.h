@@ -182,6 +182,27 @@ hipError_t tdsa_attn_d128_ragged_bwd(const void* q, const void* k,
                                      const long long* so, const long long* sd,
                                      float dropout_p, unsigned long long seed,
                                      hipStream_t stream);
+// Grouped-query, any T >= 1, no dropout: q, o, dout, dq (B, H, T, 128) and
+// lse, delta [B, H, T]; k, v, dk, dv (B, Hkv, T, 128), query head h attending
+// K/V head h / (H / Hkv). sk: strides of k and v, sdk: of dk and dv; sq of q
+// alone, so of o/dout, sd of dq. Hkv < 1 or H % Hkv != 0 returns
+// hipErrorInvalidValue and launches nothing. Hkv == H is valid and computes
+// what the ragged entry points compute.
+hipError_t tdsa_attn_d128_gqa_fwd(const void* q, const void* k, const void* v,
+                                  void* o, float* lse, long long B,
+                                  long long H, long long Hkv, int T,
+                                  float scale, const long long* sq,
+                                  const long long* sk, const long long* so,
+                                  hipStream_t stream);
+hipError_t tdsa_attn_d128_gqa_bwd(const void* q, const void* k, const void* v,
+                                  const void* o, const float* lse,
+                                  const void* dout, void* dq, void* dk,
+                                  void* dv, float* delta, long long B,
+                                  long long H, long long Hkv, int T,
+                                  float scale, const long long* sq,
+                                  const long long* sk, const long long* so,
+                                  const long long* sd, const long long* sdk,
+                                  hipStream_t stream);
 
 // ---- gemm_tn.hip ------------------------------------------------------------
 // Split count for dw = dy[M, N]^T x[M, K]; <= 0 means the shape is not taken

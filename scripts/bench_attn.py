@@ -23,6 +23,15 @@ fwd; bwd ~2.5x fwd.
                    backward), which head dim 128 took before its DROP kernels
     --sdpa         also time torch's scaled_dot_product_attention, forward
                    and backward (autograd)
+    --kv-heads N   grouped-query attention at --D 128 with N K/V heads (N
+                   divides --H, no dropout): besides the multi-head kernels at
+                   H heads (the yardstick) each round times the grouped-query
+                   entry points ("gqa") and what the same call costs without
+                   them ("expanded": K/V repeated G-fold, the multi-head
+                   kernels, dK/dV summed over each group in fp32), and prints
+                   the memory the expanded call allocates on top. "expanded"
+                   needs no grouped-query kernel, so it also runs on a --tree
+                   that has none
     --rounds N     repeat the whole set N times, the alternatives taking turns
                    within a round; with N > 1 a closing line per measurement
                    gives its range over the rounds
@@ -57,6 +66,7 @@ def main():
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--dropout", type=float, default=0.0)
     p.add_argument("--rounds", type=int, default=1)
+    p.add_argument("--kv-heads", type=int, default=0)
     p.add_argument("--tree", default=os.path.join(os.path.dirname(__file__), ".."))
     p.add_argument("--composite", action="store_true")
     p.add_argument("--composite-only", action="store_true")
@@ -88,6 +98,28 @@ def main():
         pm = torch.nn.functional.dropout(pm, p=args.dropout, training=True)
         return torch.matmul(pm, v)
 
+    Hkv = args.kv_heads
+    if Hkv:
+        assert D == 128 and not drop and H % Hkv == 0 and T >= 1
+        G = H // Hkv
+        kg, vg = (t[:, ::G].contiguous() for t in (k, v))
+        gqa_fwd = getattr(_C, "attention_d128_gqa_fwd", None)
+        gqa_bwd = getattr(_C, "attention_d128_gqa_bwd", None)
+        rag_fwd = _C.attention_d128_ragged_fwd
+        rag_bwd = _C.attention_d128_ragged_bwd
+
+        def expanded_fwd():
+            return rag_fwd(q, kg.repeat_interleave(G, dim=1),
+                           vg.repeat_interleave(G, dim=1), scale)
+
+        def expanded_bwd(o, lse, do):
+            dq, dk, dv = rag_bwd(q, kg.repeat_interleave(G, dim=1),
+                                 vg.repeat_interleave(G, dim=1), o, lse, do,
+                                 scale)
+            dk, dv = (t.view(B, Hkv, G, T, D).sum(2, dtype=torch.float32)
+                      .to(t.dtype) for t in (dk, dv))
+            return dq, dk, dv
+
     if args.composite_only:
         args.composite = True
         o, lse = att._composite_fwd(q, k, v, scale)
@@ -113,6 +145,32 @@ def main():
             note("bwd", t_bwd)
             print(f"{tag} fwd: {t_fwd*1e6:8.1f} us  {f_fwd/t_fwd/1e12:7.1f} TF/s (causal-effective)")
             print(f"{tag} bwd: {t_bwd*1e6:8.1f} us  {f_bwd/t_bwd/1e12:7.1f} TF/s (causal-effective)")
+
+        if Hkv:
+            gtag = f"{tag} Hkv{Hkv}"
+            if gqa_fwd is not None:
+                og, lseg = gqa_fwd(q, kg, vg, scale)
+                t_gf = timeit(lambda: gqa_fwd(q, kg, vg, scale), args.iters)
+                t_gb = timeit(lambda: gqa_bwd(q, kg, vg, og, lseg, do, scale),
+                              args.iters)
+                note("gqa fwd", t_gf)
+                note("gqa bwd", t_gb)
+                print(f"{gtag} gqa fwd: {t_gf*1e6:8.1f} us  bwd: {t_gb*1e6:8.1f} us")
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            oe, lsee = expanded_fwd()
+            t_ef = timeit(expanded_fwd, args.iters)
+            t_eb = timeit(lambda: expanded_bwd(oe, lsee, do), args.iters)
+            # on top of what the grouped-query call allocates: o, lse, dq and
+            # dk, dv of Hkv heads
+            peak = (torch.cuda.max_memory_allocated() - base) / 2**20
+            own = (2 * q.numel() + 2 * kg.numel()) * 2 / 2**20
+            del oe, lsee
+            note("expanded fwd", t_ef)
+            note("expanded bwd", t_eb)
+            print(f"{gtag} expanded fwd: {t_ef*1e6:8.1f} us  bwd: {t_eb*1e6:8.1f} us  "
+                  f"peak memory {peak:.0f} MiB against {own:.0f} MiB of outputs")
 
         if args.composite:
             torch.cuda.reset_peak_memory_stats()

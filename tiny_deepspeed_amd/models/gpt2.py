@@ -15,6 +15,7 @@ vocab 50304, block 1024, bias=False, selectable attention backend, returns
 
 import math
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -47,6 +48,11 @@ class GPTConfig:
     # throughput headline wins; flip on when memory-bound. Loss-only path
     # returns logits=None; inference with targets=None is unaffected.
     fused_lm_head: bool = False
+    # grouped-query attention: K/V heads, a divisor of n_head; query head h
+    # attends K/V head h // (n_head // n_kv_head). None: multi-head, today's
+    # model. "fused" backend only (HIP kernels at head dim 128 in bf16 without
+    # attention dropout, the composite elsewhere).
+    n_kv_head: Optional[int] = None
 
     @classmethod
     def gpt2_small(cls, **kw):
@@ -83,7 +89,19 @@ class CausalSelfAttention(nn.Module):
         self.head_dim = config.n_embd // config.n_head
         self.attention = config.attention
         self.dropout = config.dropout
-        self.c_attn = nn.Linear(config.n_embd, 3 * config.n_embd, bias=config.bias)
+        self.n_kv_head = config.n_kv_head
+        qkv_dim = 3 * config.n_embd
+        if self.n_kv_head is not None:
+            if self.n_kv_head < 1 or self.n_head % self.n_kv_head:
+                raise ValueError(f"n_kv_head {self.n_kv_head} must divide "
+                                 f"n_head {self.n_head}")
+            if self.attention != "fused":
+                raise ValueError(
+                    f"n_kv_head needs the \"fused\" attention backend; "
+                    f"\"{self.attention}\" splits c_attn into three equal parts")
+            # [q heads | k heads | v heads]
+            qkv_dim = (self.n_head + 2 * self.n_kv_head) * self.head_dim
+        self.c_attn = nn.Linear(config.n_embd, qkv_dim, bias=config.bias)
         self.c_proj = nn.Linear(config.n_embd, config.n_embd, bias=config.bias)
 
     def forward(self, x):
@@ -95,7 +113,7 @@ class CausalSelfAttention(nn.Module):
             # vs the reference's split+transpose+contiguous dance)
             return self.c_proj(ops.fused_causal_attention(
                 qkv, self.n_head, dropout_p=self.dropout,
-                training=self.training))
+                training=self.training, n_kv_head=self.n_kv_head))
         q, k, v = qkv.split(E, dim=2)
         # (B, T, E) -> (B, H, T, D)
         q = q.view(B, T, self.n_head, self.head_dim).transpose(1, 2).contiguous()

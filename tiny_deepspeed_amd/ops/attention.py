@@ -23,6 +23,16 @@ Head dim 128 (csrc/kernels/attention_d128.hip): bf16, with the same fused
 dropout; equal (B, H, T, p, seed) give the mask of the head-dim-64 kernels.
 CPU tensors, fp32 and other head dims use the composite autograd path, with
 torch dropout.
+
+Grouped-query attention: k and v may have Hkv heads where Hkv divides q's H;
+query head h attends K/V head h // (H // Hkv) (MQA is Hkv = 1), and the packed
+projection is (B, T, (H + 2*Hkv)*D) as [q heads | k heads | v heads]. On the
+GPU in bf16 at head dim 128 without dropout this runs the attn_d128_gqa_*
+kernels (attention_d128_gqa_fwd / _bwd, any T >= 1): K/V are read in place,
+never expanded, and dK/dV are summed over the group in fp32 registers.
+Everything else with Hkv < H (CPU, fp32, head dim 64 or any other, dropout
+> 0) takes the composite path, which broadcasts K/V over the group and sums
+dK/dV over it in fp32 before the cast. Hkv == H is the multi-head path above.
 """
 
 import math
@@ -33,8 +43,27 @@ from . import _ext
 from .autotuner import default_tuner
 
 
+def _is_gqa(q, k):
+    """k has fewer heads than q; they must divide q's."""
+    H, Hkv = q.shape[1], k.shape[1]
+    if Hkv == H:
+        return False
+    if Hkv < 1 or H % Hkv:
+        raise ValueError(f"k/v heads ({Hkv}) must divide q heads ({H})")
+    return True
+
+
+def _grouped(x, Hkv):
+    """(B, H, T, D) -> (B, Hkv, G, T, D): the query heads of each K/V head."""
+    B, H, T, D = x.shape
+    return x.reshape(B, Hkv, H // Hkv, T, D)
+
+
 def _composite_fwd(q, k, v, scale):
     qf, kf, vf = q.float(), k.float(), v.float()
+    gqa = _is_gqa(q, k)
+    if gqa:   # K/V broadcast over the group axis: no expanded copy
+        qf, kf, vf = _grouped(qf, k.shape[1]), kf.unsqueeze(2), vf.unsqueeze(2)
     T = q.shape[-2]
     s = torch.matmul(qf, kf.transpose(-2, -1)) * scale
     mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
@@ -44,11 +73,19 @@ def _composite_fwd(q, k, v, scale):
     l = p.sum(dim=-1, keepdim=True)
     o = torch.matmul(p / l, vf)
     lse = (m + l.log()).squeeze(-1)
+    if gqa:
+        o, lse = o.reshape(q.shape), lse.reshape(q.shape[:3])
     return o.to(q.dtype), lse
 
 
 def _composite_bwd(q, k, v, o, lse, do, scale):
     qf, kf, vf, of, dof = q.float(), k.float(), v.float(), o.float(), do.float()
+    gqa = _is_gqa(q, k)
+    if gqa:
+        Hkv = k.shape[1]
+        qf, of, dof = (_grouped(t, Hkv) for t in (qf, of, dof))
+        kf, vf = kf.unsqueeze(2), vf.unsqueeze(2)
+        lse = _grouped(lse.unsqueeze(-1), Hkv).squeeze(-1)
     T = q.shape[-2]
     s = torch.matmul(qf, kf.transpose(-2, -1)) * scale
     mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
@@ -60,6 +97,8 @@ def _composite_bwd(q, k, v, o, lse, do, scale):
     ds = p * (dp - delta)
     dq = torch.matmul(ds, kf) * scale
     dk = torch.matmul(ds.transpose(-2, -1), qf) * scale
+    if gqa:   # the group's sum in fp32, one rounding
+        dq, dk, dv = dq.reshape(q.shape), dk.sum(dim=2), dv.sum(dim=2)
     return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
 
 
@@ -84,6 +123,14 @@ def _kernel_supported(q):
 def _fused_dropout_supported(q):
     """Dropout is fused wherever the kernels run, at both head dims."""
     return _kernel_supported(q)
+
+
+def _gqa_kernel_supported(q):
+    """The grouped-query kernels: bf16, head dim 128, any T >= 1, no dropout
+    (csrc/kernels/attention_d128.hip). Every other grouped-query call takes
+    the composite path."""
+    return (q.dtype == torch.bfloat16 and q.shape[-1] == 128
+            and q.shape[-2] >= 1)
 
 
 def _ext_fwd(q):
@@ -158,6 +205,27 @@ def attn_bwd_packed_composite(q, k, v, o, lse, do, scale, dq, dk, dv):
     return dq, dk, dv
 
 
+# grouped-query candidates; their composite partners are the ones above
+def attn_gqa_fwd_hip(q, k, v, scale):
+    return _ext.get_ext().attention_d128_gqa_fwd(
+        q.contiguous(), k.contiguous(), v.contiguous(), scale)
+
+
+def attn_gqa_bwd_hip(q, k, v, o, lse, do, scale):
+    return _ext.get_ext().attention_d128_gqa_bwd(
+        q.contiguous(), k.contiguous(), v.contiguous(),
+        o.contiguous(), lse, do.contiguous(), scale)
+
+
+def attn_gqa_fwd_packed_hip(q, k, v, scale, o_view):
+    return _ext.get_ext().attention_d128_gqa_fwd(q, k, v, scale, o_view)
+
+
+def attn_gqa_bwd_packed_hip(q, k, v, o, lse, do, scale, dq, dk, dv):
+    return _ext.get_ext().attention_d128_gqa_bwd(q, k, v, o, lse, do, scale,
+                                                 dq, dk, dv)
+
+
 def _run(op, candidates, args, dropout_p=0.0, seed=0):
     """The one choice every kernel-path call makes. candidates[0] is the HIP
     kernel. With dropout it runs directly, with the seed that regenerates the
@@ -177,10 +245,16 @@ def _heads_view(x, n_head):
     return x.view(B, T, n_head, E // n_head).permute(0, 2, 1, 3)
 
 
-def _packed_views(qkv, n_head):
+def _packed_views(qkv, n_head, n_kv_head=None):
     """(B, T, 3*H*D) -> the three (B, H, T, D) views of the (B,T,3,H,D)
-    layout (q, k, v of a projection output; dq, dk, dv of its gradient)."""
+    layout (q, k, v of a projection output; dq, dk, dv of its gradient).
+    n_kv_head < n_head: (B, T, (H + 2*Hkv)*D) as [q heads | k heads | v heads]
+    -> views (B, H, T, D), (B, Hkv, T, D), (B, Hkv, T, D)."""
     B, T, E3 = qkv.shape
+    if n_kv_head is not None and n_kv_head != n_head:
+        D = E3 // (n_head + 2 * n_kv_head)
+        parts = qkv.split([n_head * D, n_kv_head * D, n_kv_head * D], dim=2)
+        return tuple(p.view(B, T, -1, D).permute(0, 2, 1, 3) for p in parts)
     qkv4 = qkv.view(B, T, 3, n_head, E3 // 3 // n_head)
     return tuple(qkv4[:, :, i].permute(0, 2, 1, 3) for i in range(3))
 
@@ -188,7 +262,16 @@ def _packed_views(qkv, n_head):
 class _CausalAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale, dropout_p=0.0, seed=0):
-        if _ext.use_native(q) and _kernel_supported(q):
+        ctx.gqa = _is_gqa(q, k)
+        if ctx.gqa:
+            assert dropout_p == 0.0  # caller routes GQA dropout elsewhere
+            if _ext.use_native(q) and _gqa_kernel_supported(q):
+                o, lse = _run("attn_gqa_fwd",
+                              [attn_gqa_fwd_hip, attn_fwd_composite],
+                              (q, k, v, scale))
+            else:
+                o, lse = _composite_fwd(q, k, v, scale)
+        elif _ext.use_native(q) and _kernel_supported(q):
             o, lse = _run("attn_fwd", [attn_fwd_hip, attn_fwd_composite],
                           (q, k, v, scale), dropout_p, seed)
         else:
@@ -203,7 +286,13 @@ class _CausalAttentionFn(torch.autograd.Function):
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
         args = (q, k, v, o, lse, do, ctx.scale)
-        if _ext.use_native(q) and _kernel_supported(q):
+        if ctx.gqa:
+            if _ext.use_native(q) and _gqa_kernel_supported(q):
+                dq, dk, dv = _run("attn_gqa_bwd",
+                                  [attn_gqa_bwd_hip, attn_bwd_composite], args)
+            else:
+                dq, dk, dv = _composite_bwd(*args)
+        elif _ext.use_native(q) and _kernel_supported(q):
             dq, dk, dv = _run("attn_bwd", [attn_bwd_hip, attn_bwd_composite],
                               args, *ctx.dropout)
         else:
@@ -219,15 +308,31 @@ class _FusedQKVAttentionFn(torch.autograd.Function):
     transpose-copies or cat on the hot path (the reference pays 4 transposed
     .contiguous() copies per attention plus a cat in backward through torch
     autograd).
+
+    n_kv_head < n_head (grouped-query): the packed layout is
+    (B, T, (H + 2*Hkv)*D), read and written through its strides in the same
+    way by the grouped-query kernels; no dropout on this path.
     """
 
     @staticmethod
-    def forward(ctx, qkv, n_head, scale, dropout_p=0.0, seed=0):
-        q, k, v = _packed_views(qkv, n_head)
-        B, T, E3 = qkv.shape
-        ctx.native = _ext.use_native(qkv) and _kernel_supported(q)
-        if ctx.native:
-            y = torch.empty(B, T, E3 // 3, dtype=qkv.dtype, device=qkv.device)
+    def forward(ctx, qkv, n_head, scale, dropout_p=0.0, seed=0,
+                n_kv_head=None):
+        q, k, v = _packed_views(qkv, n_head, n_kv_head)
+        B, T, _ = qkv.shape
+        E = n_head * q.shape[-1]
+        ctx.gqa = _is_gqa(q, k)
+        if ctx.gqa:
+            assert dropout_p == 0.0  # caller routes GQA dropout elsewhere
+            ctx.native = _ext.use_native(qkv) and _gqa_kernel_supported(q)
+        else:
+            ctx.native = _ext.use_native(qkv) and _kernel_supported(q)
+        if ctx.native and ctx.gqa:
+            y = torch.empty(B, T, E, dtype=qkv.dtype, device=qkv.device)
+            o, lse = _run("attn_gqa_fwd_packed",
+                          [attn_gqa_fwd_packed_hip, attn_fwd_packed_composite],
+                          (q, k, v, scale, _heads_view(y, n_head)))
+        elif ctx.native:
+            y = torch.empty(B, T, E, dtype=qkv.dtype, device=qkv.device)
             o, lse = _run("attn_fwd_packed",
                           [attn_fwd_packed_hip, attn_fwd_packed_composite],
                           (q, k, v, scale, _heads_view(y, n_head)),
@@ -235,9 +340,10 @@ class _FusedQKVAttentionFn(torch.autograd.Function):
         else:
             o, lse = _composite_fwd(q.contiguous(), k.contiguous(),
                                     v.contiguous(), scale)
-            y = o.permute(0, 2, 1, 3).reshape(B, T, E3 // 3)
+            y = o.permute(0, 2, 1, 3).reshape(B, T, E)
         ctx.save_for_backward(qkv, y, lse)
         ctx.n_head = n_head
+        ctx.n_kv_head = n_kv_head
         ctx.scale = scale
         ctx.dropout = (dropout_p, seed)
         return y
@@ -246,10 +352,16 @@ class _FusedQKVAttentionFn(torch.autograd.Function):
     def backward(ctx, dy):
         qkv, y, lse = ctx.saved_tensors
         n_head = ctx.n_head
-        q, k, v = _packed_views(qkv, n_head)
+        q, k, v = _packed_views(qkv, n_head, ctx.n_kv_head)
         o_view = _heads_view(y, n_head)
         do_view = _heads_view(dy.contiguous(), n_head)
-        if ctx.native:
+        if ctx.native and ctx.gqa:
+            dqkv = torch.empty_like(qkv)
+            _run("attn_gqa_bwd_packed",
+                 [attn_gqa_bwd_packed_hip, attn_bwd_packed_composite],
+                 (q, k, v, o_view, lse, do_view, ctx.scale,
+                  *_packed_views(dqkv, n_head, ctx.n_kv_head)))
+        elif ctx.native:
             dqkv = torch.empty_like(qkv)
             _run("attn_bwd_packed",
                  [attn_bwd_packed_hip, attn_bwd_packed_composite],
@@ -260,19 +372,27 @@ class _FusedQKVAttentionFn(torch.autograd.Function):
                 q.contiguous(), k.contiguous(), v.contiguous(),
                 o_view.contiguous(), lse, do_view.contiguous(), ctx.scale)
             dqkv = torch.cat(
-                [g.permute(0, 2, 1, 3).reshape(y.shape) for g in grads], dim=2)
-        return dqkv, None, None, None, None
+                [g.permute(0, 2, 1, 3).flatten(2) for g in grads], dim=2)
+        return dqkv, None, None, None, None, None
 
 
 def fused_causal_attention(qkv, n_head, scale=None, dropout_p=0.0,
-                           training=False):
-    """qkv: (B, T, 3E) packed projection output. Returns (B, T, E)."""
+                           training=False, n_kv_head=None):
+    """qkv: (B, T, 3E) packed projection output. Returns (B, T, E).
+    n_kv_head (grouped-query): qkv is (B, T, (n_head + 2*n_kv_head)*D) as
+    [q heads | k heads | v heads]; None or n_head is the multi-head layout."""
+    if n_kv_head == n_head:
+        n_kv_head = None
+    if n_kv_head is not None and (n_kv_head < 1 or n_head % n_kv_head):
+        raise ValueError(f"n_kv_head {n_kv_head} must divide n_head {n_head}")
     if scale is None:
-        scale = 1.0 / math.sqrt(qkv.shape[-1] // 3 // n_head)
+        scale = 1.0 / math.sqrt(
+            qkv.shape[-1] // (n_head + 2 * (n_kv_head or n_head)))
     p = dropout_p if training else 0.0
     if p > 0.0:
-        q, k, v = _packed_views(qkv, n_head)
-        if _ext.use_native(qkv) and _fused_dropout_supported(q):
+        q, k, v = _packed_views(qkv, n_head, n_kv_head)
+        if (n_kv_head is None and _ext.use_native(qkv)
+                and _fused_dropout_supported(q)):
             # fused in-kernel dropout
             return _FusedQKVAttentionFn.apply(qkv, n_head, scale, p,
                                               _draw_seed())
@@ -280,6 +400,9 @@ def fused_causal_attention(qkv, n_head, scale=None, dropout_p=0.0,
         y = causal_attention(q.contiguous(), k.contiguous(), v.contiguous(),
                              scale, p, training)
         return y.transpose(1, 2).reshape(y.shape[0], y.shape[2], -1)
+    if n_kv_head is not None:
+        return _FusedQKVAttentionFn.apply(qkv, n_head, scale, 0.0, 0,
+                                          n_kv_head)
     return _FusedQKVAttentionFn.apply(qkv, n_head, scale)
 
 
@@ -289,10 +412,16 @@ def causal_attention(q, k, v, scale=None, dropout_p=0.0, training=False):
         scale = 1.0 / math.sqrt(k.shape[-1])
     p = dropout_p if training else 0.0
     if p > 0.0:
-        if _ext.use_native(q) and _fused_dropout_supported(q):
+        gqa = _is_gqa(q, k)
+        if (not gqa and _ext.use_native(q)
+                and _fused_dropout_supported(q)):
             # fused in-kernel dropout
             return _CausalAttentionFn.apply(q, k, v, scale, p, _draw_seed())
-        # CPU, unsupported dtypes and head dims: composite autograd path
+        # CPU, unsupported dtypes and head dims, grouped-query: composite
+        # autograd path (autograd sums dK/dV over the group)
+        if gqa:
+            G = q.shape[1] // k.shape[1]
+            k, v = (t.repeat_interleave(G, dim=1) for t in (k, v))
         T = q.shape[-2]
         s = torch.matmul(q, k.transpose(-2, -1)) * scale
         mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
