@@ -258,6 +258,105 @@ std::vector<int64_t> layernorm_rowwave_geometry(int64_t M, int64_t N,
   return {tdsa_ln_bwd_dx_stripes((int)M, (int)N, is_bf16), fw, fd, bd, bound};
 }
 
+// ---- rmsnorm --------------------------------------------------------------
+// (stripes G, fwd units, fwd depth, bwd depth, span, bound) of the RMSNorm
+// kernels for an (M, N) problem; all 0 where the shape is not routed (bf16,
+// N % 8 == 0, 8 <= N <= 8192 is).
+std::vector<int64_t> rmsnorm_geometry(int64_t M, int64_t N, bool is_bf16) {
+  int g = 0, fu = 0, fd = 0, bd = 0, span = 0, bound = 0;
+  if (M >= 0 && M <= INT_MAX && N >= 0 && N <= INT_MAX)
+    tdsa_rms_geometry((int)M, (int)N, is_bf16, &g, &fu, &fd, &bd, &span,
+                      &bound);
+  return {g, fu, fd, bd, span, bound};
+}
+
+// The kernels take routed shapes only and there is no second path: refuse
+// the call before anything is allocated.
+int rms_stripes(const char* op, int M, int N, int flag) {
+  const auto geo = rmsnorm_geometry(M, N, flag != 0);
+  TORCH_CHECK(geo[4] > 0, op, ": x must be bfloat16 with 8 <= N <= 8192 and "
+              "N % 8 == 0, got ", flag ? "bfloat16" : "float32", " N = ", N);
+  return (int)geo[0];
+}
+
+// -> [y, rstd], or [y, rstd, h] with res (h = x + res, normalised).
+std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps,
+                                    c10::optional<at::Tensor> res) {
+  const char* op = "rmsnorm_fwd";
+  int M, N;
+  ln_rows(op, x, &M, &N);
+  const int flag = check_call(op, {{"x", x, {}, kAny}, {"w", w, {}, N},
+                                   {"res", res, {}, x.numel()}});
+  rms_stripes(op, M, N, flag);
+  auto y = at::empty_like(x);
+  auto row_sizes = x.sizes().vec();
+  row_sizes.pop_back();
+  auto rstd = at::empty(row_sizes, x.options().dtype(at::kFloat));
+  at::Tensor h;
+  void* res_p = nullptr;
+  void* h_p = nullptr;
+  if (res.has_value()) {
+    h = at::empty_like(x);
+    res_p = res->data_ptr();
+    h_p = h.data_ptr();
+  }
+  check_hip(tdsa_rms_fwd(x.data_ptr(), res_p, h_p, w.data_ptr(), y.data_ptr(),
+                         rstd.data_ptr<float>(), M, N, (float)eps, flag,
+                         cur_stream()),
+            op);
+  if (res.has_value()) return {y, rstd, h};
+  return {y, rstd};
+}
+
+// -> [dx, pdw]; x is what the forward normalised (its h in the residual form).
+std::vector<at::Tensor> rmsnorm_bwd_dx(at::Tensor dy, at::Tensor x,
+                                       at::Tensor w, at::Tensor rstd,
+                                       c10::optional<at::Tensor> dh) {
+  const char* op = "rmsnorm_bwd_dx";
+  int M, N;
+  ln_rows(op, x, &M, &N);
+  const int flag = check_call(op, {{"x", x, {}, kAny},
+                                   {"dy", dy, {}, x.numel()},
+                                   {"w", w, {}, N},
+                                   {"rstd", rstd, at::kFloat, M, true},
+                                   {"dh", dh, {}, x.numel(), true}});
+  const int G = rms_stripes(op, M, N, flag);
+  auto dx = at::empty_like(x);
+  auto pdw = at::empty({G, N}, x.options().dtype(at::kFloat));
+  auto rstdc = rstd.contiguous();
+  at::Tensor dhc;
+  void* dh_p = nullptr;
+  if (dh.has_value()) {
+    dhc = dh->contiguous();
+    dh_p = dhc.data_ptr();
+  }
+  check_hip(tdsa_rms_bwd_dx(dy.data_ptr(), dh_p, x.data_ptr(), w.data_ptr(),
+                            rstdc.data_ptr<float>(), dx.data_ptr(),
+                            pdw.data_ptr<float>(), M, N, flag, cur_stream()),
+            op);
+  return {dx, pdw};
+}
+
+// dtype: output dtype of dw (float32 or bfloat16, rounded in-kernel from the
+// fp32 sums); fp32 when absent.
+at::Tensor rmsnorm_bwd_dw(at::Tensor pdw,
+                          c10::optional<at::ScalarType> dtype) {
+  const char* op = "rmsnorm_bwd_dw";
+  check_call(op, {{"pdw", pdw, at::kFloat, kAny}});
+  TORCH_CHECK(pdw.dim() == 2 && pdw.size(0) > 0 && pdw.size(1) > 0, op,
+              ": pdw must be a non-empty 2-D tensor, got ", pdw.sizes());
+  const at::ScalarType out = dtype.value_or(at::kFloat);
+  TORCH_CHECK(out == at::kFloat || out == at::kBFloat16, op,
+              ": dtype must be float32 or bfloat16, got ", out);
+  const int G = as_int(op, "G", pdw.size(0));
+  const int N = as_int(op, "N", pdw.size(1));
+  auto dw = at::empty({N}, pdw.options().dtype(out));
+  check_hip(tdsa_rms_dw_reduce(pdw.data_ptr<float>(), dw.data_ptr(), G, N,
+                               out == at::kBFloat16, cur_stream()),
+            op);
+  return dw;
+}
+
 // ---- elementwise ----------------------------------------------------------
 at::Tensor gelu_fwd(at::Tensor x) {
   const int flag = check_call("gelu_fwd", {{"x", x, {}, kAny}});
@@ -941,6 +1040,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("pdb"), py::arg("dtype") = py::none());
   mod.def("layernorm_rowwave_geometry", &layernorm_rowwave_geometry,
           py::arg("M"), py::arg("N"), py::arg("is_bf16") = true);
+  mod.def("rmsnorm_fwd", &rmsnorm_fwd, py::arg("x"), py::arg("w"),
+          py::arg("eps"), py::arg("res") = py::none());
+  mod.def("rmsnorm_bwd_dx", &rmsnorm_bwd_dx, py::arg("dy"), py::arg("x"),
+          py::arg("w"), py::arg("rstd"), py::arg("dh") = py::none());
+  mod.def("rmsnorm_bwd_dw", &rmsnorm_bwd_dw, py::arg("pdw"),
+          py::arg("dtype") = py::none());
+  mod.def("rmsnorm_geometry", &rmsnorm_geometry, py::arg("M"), py::arg("N"),
+          py::arg("is_bf16") = true);
   mod.def("gelu_fwd", &gelu_fwd);
   mod.def("gelu_bwd", &gelu_bwd);
   mod.def("column_sum", &column_sum);

@@ -60,6 +60,31 @@ hipError_t tdsa_ln_bwd_dwdb(const float* pdw, const float* pdb, void* dw,
                             void* db, int G, int N, int out_bf16,
                             hipStream_t stream);
 
+// ---- rmsnorm.hip ------------------------------------------------------------
+// Routed shapes only: bf16, N % 8 == 0, 8 <= N <= 8192 (a wave per row up to
+// 2048, a workgroup per row above). Any other shape returns
+// hipErrorInvalidValue and launches nothing.
+// x, y [M, N]; w [N]; rstd fp32 [M]. res/h: optional fused residual (h = x +
+// res is written and normalised); both null for the plain form.
+hipError_t tdsa_rms_fwd(const void* x, const void* res, void* h, const void* w,
+                        void* y, float* rstd, int M, int N, float eps,
+                        int is_bf16, hipStream_t stream);
+// x: what the forward normalised (its h in the residual form). dh: optional
+// residual-stream gradient added into dx. pdw fp32 [G, N], G the stripe count
+// of tdsa_rms_geometry, receives the dw partials (need not be initialised).
+hipError_t tdsa_rms_bwd_dx(const void* dy, const void* dh, const void* x,
+                           const void* w, const float* rstd, void* dx,
+                           float* pdw, int M, int N, int is_bf16,
+                           hipStream_t stream);
+// dw [N] = column sums of pdw [G, N]; out_bf16 picks its dtype. Any N.
+hipError_t tdsa_rms_dw_reduce(const float* pdw, void* dw, int G, int N,
+                              int out_bf16, hipStream_t stream);
+// Launch geometry of an (M, N) problem: stripe count G (= backward units),
+// forward units, the two batch depths, the span (waves per row: 1 or 4) and
+// the last routed N. All 0 when the shape is not routed.
+void tdsa_rms_geometry(int M, int N, int is_bf16, int* stripes, int* fwd_units,
+                       int* fwd_depth, int* bwd_depth, int* span, int* bound);
+
 // ---- elementwise.hip --------------------------------------------------------
 // y[n] = gelu(x[n]), any n.
 hipError_t tdsa_gelu_fwd(const void* x, void* y, long long n, int is_bf16,

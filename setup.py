@@ -17,6 +17,7 @@ from torch.utils.cpp_extension import BuildExtension, CUDAExtension
 SOURCES = [
     "csrc/bind.cpp",
     "csrc/kernels/layernorm.hip",
+    "csrc/kernels/rmsnorm.hip",
     "csrc/kernels/elementwise.hip",
     "csrc/kernels/embedding.hip",
     "csrc/kernels/cross_entropy.hip",

@@ -53,6 +53,18 @@ class GPTConfig:
     # model. "fused" backend only (HIP kernels at head dim 128 in bf16 without
     # attention dropout, the composite elsewhere).
     n_kv_head: Optional[int] = None
+    # "layernorm": nn.LayerNorm (today's model and state-dict keys);
+    # "rmsnorm": nn.RMSNorm(n_embd, eps=1e-5) for ln_1, ln_2 and ln_f (weight
+    # only; HIP kernels for bf16 widths up to 8192 once wrapped).
+    norm: str = "layernorm"
+
+    def make_norm(self):
+        if self.norm == "layernorm":
+            return nn.LayerNorm(self.n_embd)
+        if self.norm == "rmsnorm":
+            return nn.RMSNorm(self.n_embd, eps=1e-5)
+        raise ValueError(f"unknown norm \"{self.norm}\": expected "
+                         "\"layernorm\" or \"rmsnorm\"")
 
     @classmethod
     def gpt2_small(cls, **kw):
@@ -147,9 +159,9 @@ class MLP(nn.Module):
 class Block(nn.Module):
     def __init__(self, config):
         super().__init__()
-        self.ln_1 = nn.LayerNorm(config.n_embd)
+        self.ln_1 = config.make_norm()
         self.attn = CausalSelfAttention(config)
-        self.ln_2 = nn.LayerNorm(config.n_embd)
+        self.ln_2 = config.make_norm()
         self.mlp = MLP(config)
         self.resid_dropout = config.resid_dropout
 
@@ -190,7 +202,7 @@ class GPT2Model(nn.Module):
             wte=nn.Embedding(config.vocab_size, config.n_embd),
             wpe=nn.Embedding(config.block_size, config.n_embd),
             h=nn.ModuleList(Block(config) for _ in range(config.n_layer)),
-            ln_f=nn.LayerNorm(config.n_embd),
+            ln_f=config.make_norm(),
         ))
         self.lm_head = nn.Linear(config.n_embd, config.vocab_size, bias=False)
         self.apply(self._init_weights)

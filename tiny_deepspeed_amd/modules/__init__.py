@@ -6,7 +6,7 @@ reference's empty stubs (SURVEY.md component #13).
 """
 
 from .linear import Linear
-from .normalization import LayerNorm
+from .normalization import LayerNorm, RMSNorm
 from .embedding import Embedding
 
-__all__ = ["Linear", "LayerNorm", "Embedding"]
+__all__ = ["Linear", "LayerNorm", "RMSNorm", "Embedding"]

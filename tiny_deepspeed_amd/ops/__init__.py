@@ -15,6 +15,7 @@ from .linear import (
 from .layernorm import (layernorm_fwd, layernorm_fwd_res, layernorm_dx,
                         layernorm_dwdb, layernorm_fwd_res_dropout,
                         layernorm_dx_dropout, dropout_keep_mask, dropout_grad)
+from .rmsnorm import rmsnorm_fwd, rmsnorm_fwd_res, rmsnorm_dx, rmsnorm_dw
 from .embedding import embedding_forward, embedding_weight_grad
 from .gelu import gelu, gelu_fwd, gelu_bwd
 from .attention import causal_attention, fused_causal_attention
@@ -29,6 +30,7 @@ __all__ = [
     "layernorm_fwd", "layernorm_fwd_res", "layernorm_dx", "layernorm_dwdb",
     "layernorm_fwd_res_dropout", "layernorm_dx_dropout", "dropout_keep_mask",
     "dropout_grad",
+    "rmsnorm_fwd", "rmsnorm_fwd_res", "rmsnorm_dx", "rmsnorm_dw",
     "embedding_forward", "embedding_weight_grad",
     "gelu", "gelu_fwd", "gelu_bwd",
     "causal_attention", "fused_causal_attention",

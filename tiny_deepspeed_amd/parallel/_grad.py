@@ -87,5 +87,6 @@ def strategy_swap_map(mode, *mixins):
                         {"_mode": mode})
         for torch_cls, base_cls in ((nn.Linear, base.Linear),
                                     (nn.LayerNorm, base.LayerNorm),
+                                    (nn.RMSNorm, base.RMSNorm),
                                     (nn.Embedding, base.Embedding))
     }

@@ -34,6 +34,9 @@ def _init_args_of(mod):
         return dict(normalized_shape=mod.normalized_shape, eps=mod.eps,
                     elementwise_affine=mod.elementwise_affine,
                     bias=mod.bias is not None)
+    if isinstance(mod, nn.RMSNorm):
+        return dict(normalized_shape=mod.normalized_shape, eps=mod.eps,
+                    elementwise_affine=mod.elementwise_affine)
     if isinstance(mod, nn.Embedding):
         return dict(num_embeddings=mod.num_embeddings,
                     embedding_dim=mod.embedding_dim,
@@ -85,7 +88,7 @@ def check_all_params_wrapped(model):
         if not getattr(p, "_tdsa_wrapped", False):
             raise RuntimeError(
                 f"parameter {name} belongs to an unsupported module type; "
-                "only Linear/LayerNorm/Embedding parameters are handled"
+                "only Linear/LayerNorm/RMSNorm/Embedding parameters are handled"
             )
 
 
@@ -158,5 +161,6 @@ class Single(ModelWrapper):
     swap_map = {
         nn.Linear: base_modules.Linear,
         nn.LayerNorm: base_modules.LayerNorm,
+        nn.RMSNorm: base_modules.RMSNorm,
         nn.Embedding: base_modules.Embedding,
     }

@@ -119,6 +119,8 @@ def _materialize(mod, pname, shape, dtype, device):
             nn.init.ones_(t)
         else:
             nn.init.zeros_(t)
+    elif isinstance(mod, nn.RMSNorm):
+        nn.init.ones_(t)
     elif isinstance(mod, nn.Embedding):
         nn.init.normal_(t)
     else:
