@@ -391,6 +391,44 @@ at::Tensor column_sum(at::Tensor dy) {
   return out;
 }
 
+// ---- swiglu ---------------------------------------------------------------
+// Rows M and half width F of a packed gate/up tensor gu (M, 2F).
+void swiglu_rows(const char* op, const at::Tensor& gu, int* M, int* F) {
+  TORCH_CHECK(gu.dim() == 2 && gu.size(0) > 0 && gu.size(1) > 0 &&
+                  gu.size(1) % 2 == 0,
+              op, ": gu must be a non-empty 2-D (M, 2F) tensor with an even "
+              "last dim, got ", gu.sizes());
+  *M = as_int(op, "M", gu.size(0));
+  *F = as_int(op, "F", gu.size(1) / 2);
+}
+
+// y (M, F) = silu(gu[:, :F]) * gu[:, F:].
+at::Tensor swiglu_fwd(at::Tensor gu) {
+  const char* op = "swiglu_fwd";
+  int M, F;
+  swiglu_rows(op, gu, &M, &F);
+  const int flag = check_call(op, {{"gu", gu, {}, kAny}});
+  auto y = at::empty({(long long)M, (long long)F}, gu.options());
+  check_hip(tdsa_swiglu_fwd(gu.data_ptr(), y.data_ptr(), M, F, flag,
+                            cur_stream()),
+            op);
+  return y;
+}
+
+// dgu (M, 2F) = [dgate | dup] for dy of M * F elements.
+at::Tensor swiglu_bwd(at::Tensor dy, at::Tensor gu) {
+  const char* op = "swiglu_bwd";
+  int M, F;
+  swiglu_rows(op, gu, &M, &F);
+  const int flag = check_call(op, {{"gu", gu, {}, kAny},
+                                   {"dy", dy, {}, (int64_t)M * F}});
+  auto dgu = at::empty_like(gu);
+  check_hip(tdsa_swiglu_bwd(dy.data_ptr(), gu.data_ptr(), dgu.data_ptr(), M, F,
+                            flag, cur_stream()),
+            op);
+  return dgu;
+}
+
 // ---- embedding ------------------------------------------------------------
 at::Tensor embedding_fwd(at::Tensor weight, at::Tensor idx) {
   const char* op = "embedding_fwd";
@@ -1051,6 +1089,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gelu_fwd", &gelu_fwd);
   mod.def("gelu_bwd", &gelu_bwd);
   mod.def("column_sum", &column_sum);
+  mod.def("swiglu_fwd", &swiglu_fwd, py::arg("gu"));
+  mod.def("swiglu_bwd", &swiglu_bwd, py::arg("dy"), py::arg("gu"));
   mod.def("embedding_fwd", &embedding_fwd);
   mod.def("embedding_bwd", &embedding_bwd);
   mod.def("cross_entropy_fwd", &cross_entropy_fwd);

@@ -97,6 +97,18 @@ hipError_t tdsa_gelu_bwd(const void* dy, const void* x, void* dx, long long n,
 hipError_t tdsa_column_sum(const void* dy, float* out32, void* out, int M,
                            int N, int is_bf16, hipStream_t stream);
 
+// ---- swiglu.hip -------------------------------------------------------------
+// gu [M, 2F] packed: gate = gu[:, :F], up = gu[:, F:]. y [M, F] =
+// silu(gate) * up. Any M >= 1 and F >= 1 (16-byte vectors where they divide F,
+// single elements otherwise); M < 1 or F < 1 returns hipErrorInvalidValue and
+// launches nothing. y must not overlap gu.
+hipError_t tdsa_swiglu_fwd(const void* gu, void* y, int M, int F, int is_bf16,
+                           hipStream_t stream);
+// dy [M, F]; dgu [M, 2F] receives [dgate | dup], every element written,
+// recomputed from gu alone. dgu must not overlap dy or gu.
+hipError_t tdsa_swiglu_bwd(const void* dy, const void* gu, void* dgu, int M,
+                           int F, int is_bf16, hipStream_t stream);
+
 // ---- embedding.hip ----------------------------------------------------------
 // out [R, D] = weight[idx[r]]; every idx must be a valid row of weight.
 hipError_t tdsa_embedding_fwd(const void* weight, const long long* idx,

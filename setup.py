@@ -19,6 +19,7 @@ SOURCES = [
     "csrc/kernels/layernorm.hip",
     "csrc/kernels/rmsnorm.hip",
     "csrc/kernels/elementwise.hip",
+    "csrc/kernels/swiglu.hip",
     "csrc/kernels/embedding.hip",
     "csrc/kernels/cross_entropy.hip",
     "csrc/kernels/optim.hip",

@@ -5,9 +5,10 @@ architecture family and config fields: 12L/12H/768d GPT-2 small by default,
 vocab 50304, block 1024, bias=False, selectable attention backend, returns
 (logits, loss)). Differences by design:
 
-- attention, GELU and the loss go through tiny_deepspeed_amd.ops — on GPU
-  these are the hand-written CDNA4 kernels (fused causal attention,
-  elementwise GELU, fused cross-entropy); on CPU the torch fallbacks.
+- attention, GELU (or SwiGLU, ``mlp="swiglu"``) and the loss go through
+  tiny_deepspeed_amd.ops — on GPU these are the hand-written CDNA4 kernels
+  (fused causal attention, elementwise GELU / SwiGLU, fused cross-entropy);
+  on CPU the torch fallbacks.
 - nn.Linear / nn.LayerNorm / nn.Embedding are used raw so the parallel
   wrappers can swap them for strategy modules (SURVEY.md component #14).
 - presets for small/medium/large/xl support the BASELINE.json configs.
@@ -57,6 +58,28 @@ class GPTConfig:
     # "rmsnorm": nn.RMSNorm(n_embd, eps=1e-5) for ln_1, ln_2 and ln_f (weight
     # only; HIP kernels for bf16 widths up to 8192 once wrapped).
     norm: str = "layernorm"
+    # "gelu": c_fc -> GELU -> c_proj (today's model and state-dict shapes);
+    # "swiglu": the gated SiLU MLP. c_fc projects to 2 * hidden, rows
+    # [0, hidden) the gate and [hidden, 2 * hidden) the up projection, and
+    # c_proj takes silu(gate) * up (one HIP kernel each way on GPU).
+    mlp: str = "gelu"
+    # MLP width. None: 4 * n_embd for "gelu"; for "swiglu" 8 * n_embd / 3
+    # rounded up to a multiple of 256 (768 -> 2048, 1024 -> 2816,
+    # 4096 -> 11008), about the parameter count of the GELU MLP.
+    mlp_hidden: Optional[int] = None
+
+    def mlp_width(self):
+        if self.mlp not in ("gelu", "swiglu"):
+            raise ValueError(f"unknown mlp \"{self.mlp}\": expected "
+                             "\"gelu\" or \"swiglu\"")
+        if self.mlp_hidden is not None:
+            if self.mlp_hidden < 1:
+                raise ValueError(f"mlp_hidden must be >= 1, got "
+                                 f"{self.mlp_hidden}")
+            return self.mlp_hidden
+        if self.mlp == "gelu":
+            return 4 * self.n_embd
+        return -(-8 * self.n_embd // (3 * 256)) * 256
 
     def make_norm(self):
         if self.norm == "layernorm":
@@ -149,11 +172,15 @@ class CausalSelfAttention(nn.Module):
 class MLP(nn.Module):
     def __init__(self, config):
         super().__init__()
-        self.c_fc = nn.Linear(config.n_embd, 4 * config.n_embd, bias=config.bias)
-        self.c_proj = nn.Linear(4 * config.n_embd, config.n_embd, bias=config.bias)
+        hidden = config.mlp_width()
+        self.gated = config.mlp == "swiglu"
+        fc_out = 2 * hidden if self.gated else hidden
+        self.c_fc = nn.Linear(config.n_embd, fc_out, bias=config.bias)
+        self.c_proj = nn.Linear(hidden, config.n_embd, bias=config.bias)
 
     def forward(self, x):
-        return self.c_proj(ops.gelu(self.c_fc(x)))
+        act = ops.swiglu if self.gated else ops.gelu
+        return self.c_proj(act(self.c_fc(x)))
 
 
 class Block(nn.Module):

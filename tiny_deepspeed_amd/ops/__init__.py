@@ -2,8 +2,8 @@
 
 Public surface mirrors the reference's ops re-exports
 (``/root/reference/tiny_deepspeed/core/module/ops/__init__.py:4-18``) plus
-the additional fused hot ops the MI355X build hand-writes (gelu, attention,
-cross-entropy, fused optimizer updates).
+the additional fused hot ops the MI355X build hand-writes (gelu, swiglu,
+attention, cross-entropy, fused optimizer updates).
 """
 
 from .linear import (
@@ -18,6 +18,7 @@ from .layernorm import (layernorm_fwd, layernorm_fwd_res, layernorm_dx,
 from .rmsnorm import rmsnorm_fwd, rmsnorm_fwd_res, rmsnorm_dx, rmsnorm_dw
 from .embedding import embedding_forward, embedding_weight_grad
 from .gelu import gelu, gelu_fwd, gelu_bwd
+from .swiglu import swiglu, swiglu_fwd, swiglu_bwd
 from .attention import causal_attention, fused_causal_attention
 from .cross_entropy import cross_entropy, cross_entropy_fwd, cross_entropy_bwd
 from .optim_ops import adamw_step, sgd_step, grad_sumsq, clip_coef
@@ -33,6 +34,7 @@ __all__ = [
     "rmsnorm_fwd", "rmsnorm_fwd_res", "rmsnorm_dx", "rmsnorm_dw",
     "embedding_forward", "embedding_weight_grad",
     "gelu", "gelu_fwd", "gelu_bwd",
+    "swiglu", "swiglu_fwd", "swiglu_bwd",
     "causal_attention", "fused_causal_attention",
     "cross_entropy", "cross_entropy_fwd", "cross_entropy_bwd",
     "adamw_step", "sgd_step", "grad_sumsq", "clip_coef",
